@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- frame x center RMSD pairs/s of the k-centers hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps S] [--warmup W]
+    python bench.py [--gpus N] [--steps S] [--warmup W] [--dump-outputs DIR]
 
 Workload: BASELINE.json configs[1] -- 1,000,000 synthetic frames x 300 atoms,
-5000 centers -- whatever S is.  The timed region is the WHOLE fit, from the
-untouched state (every distance +inf) to 5000 centers; a "step" is
-5000 / S consecutive centers of it (250 with the driver's --steps 20; one
-center with --steps 5000), each center being its RMSD to every frame, the
-strict-< update and the farthest-point reduction: n_frames pairs.
-`value` = n_frames * 5000 / elapsed; `ms_per_step` = elapsed / S.
-The W warm-up steps are W * (5000 / S) centers of a throw-away fit from the
-same untouched state; the state is reset before the clock starts.
+5000 centers.  A timed STEP is one WHOLE fit, from the untouched state (every
+distance +inf) to 5000 centers, each center being its RMSD to every frame, the
+strict-< update and the farthest-point reduction: n_frames pairs.  The S steps
+are S such fits one after another; the state is reset before each, outside
+the clock.  `value` = n_frames * 5000 * S / elapsed; `ms_per_step` =
+elapsed / S, so S steps take S times as long as one.  The W warm-up steps are
+W throw-away fits of the same kind.
+
+--dump-outputs DIR: after the timed steps, what the last one handed its caller
+(dump_outputs) is written as DIR/<name>.npy.  The frames are seeded by --seed,
+so the same arguments give the same inputs on every run and two builds can be
+compared output for output.
 
 N > 1: `python bench.py --gpus N` starts N worker processes itself (one per
 GPU, RCCL) before touching any GPU; under `torch.distributed.run` the ranks
@@ -125,6 +129,8 @@ def parse():
     p.add_argument("--sharded", action="store_true",
                    help="use the torch.distributed driver even with one rank "
                         "(exercises the RCCL path on a 1-GPU box)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/*.npy")
     return p.parse_args()
 
 
@@ -638,6 +644,46 @@ def one_center_leg(store, args, n_local, launches=48):
                     "frames, 12 A + 16 algorithmic bytes per pair"}
 
 
+DUMP_MAX_FRAMES = 1 << 21      # per-frame arrays of --dump-outputs: at most 40 MB
+DUMP_MAX_CENTERS = 1 << 20     # center arrays: at most 12 MB
+
+
+def dump_outputs(path, store, idx, cdist, lo, n_local, n_total, use_dist, rank):
+    """--dump-outputs: what the last timed fit handed its caller, as .npy files
+    in `path`: center_indices (float64 [k]); center_distances (float32 [k - 1]:
+    the distance at which centers 2 .. k were chosen, i.e. the farthest frame's
+    distance to the centers before it -- the first center's entry is the +inf
+    every fit starts from, not a computed value, and is left out); and per
+    frame its label (float64) and float32 distance to that center (KCenters'
+    labels_ / distances_).  Above DUMP_MAX_FRAMES frames the per-frame arrays are a fixed
+    sample (seed 0, in frame order) whose global frame numbers are in
+    frame_index.npy; above DUMP_MAX_CENTERS centers, the first ones.
+    Collective with N > 1: every rank sends its block's part to rank 0."""
+    d, a = store.download_state()
+    sel = None
+    if n_total > DUMP_MAX_FRAMES:
+        sel = np.sort(np.random.RandomState(0).choice(n_total, DUMP_MAX_FRAMES,
+                                                      replace=False))
+        mine = sel[(sel >= lo) & (sel < lo + n_local)] - lo
+        d, a = d[mine], a[mine]
+    parts = [(d, a)]
+    if use_dist:
+        # (the ranks' blocks are contiguous and in rank order)
+        import torch.distributed as dist
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (d, a))
+    if rank != 0:
+        return
+    out = {"center_indices": np.asarray(idx[:DUMP_MAX_CENTERS], dtype=np.float64),
+           "center_distances": np.asarray(cdist[1:DUMP_MAX_CENTERS], dtype=np.float32),
+           "labels": np.concatenate([p[1] for p in parts]).astype(np.float64),
+           "distances": np.concatenate([p[0] for p in parts]).astype(np.float32)}
+    if sel is not None:
+        out["frame_index"] = sel.astype(np.float64)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -655,9 +701,8 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps >= 1 and --warmup >= 0")
-    if args.steps > args.centers:
-        raise SystemExit("--steps %d > --centers %d: a step is at least one "
-                         "center" % (args.steps, args.centers))
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
 
     import torch
     import torch.distributed as dist
@@ -686,10 +731,8 @@ def main():
                 "nccl", rank=rank, world_size=world,
                 device_id=torch.device("cuda", local_rank))
 
-    # a step = cps consecutive centers of the one fit
-    cps = max(1, args.centers // args.steps)
-    centers_total = cps * args.steps
-    warm_centers = min(cps * args.warmup, centers_total)
+    # a step = one whole fit of centers_total centers
+    centers_total = args.centers
     data_lo, lo, n_local = rank_frames(args, rank, world)
     n_stream = stream_length(args, rank, world)
     n_total = args.frames if (world == 1 or args.scaling == "strong") \
@@ -781,30 +824,32 @@ def main():
     run(min(centers_total, 2000))
     t_wake = time.perf_counter() - t0
 
-    # ---- warm-up: W steps of a throw-away fit ----------------------------------
-    if warm_centers:
-        run(warm_centers)
+    # ---- warm-up: W throw-away fits ----------------------------------------------
+    for _ in range(args.warmup):
+        run(centers_total)
 
-    # ---- timed region: the whole fit, --steps steps of cps centers --------------
-    store.reset_state()
-    store.sync()
+    # ---- timed region: --steps whole fits, each from the untouched state ----------
     store.timing_begin(sample_every=2, max_samples=1024)
-    if use_dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    if use_dist:
-        with torch.cuda.stream(tstream):
-            idx, _ = sharded.kcenters_sharded(shard, 0, centers_total, 0.0,
-                                              fresh=True)
-    else:
-        idx, _, _ = store.kcenters_run(0, centers_total, 0.0)
-    torch.cuda.synchronize()
-    if use_dist:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
-    if len(idx) != centers_total:
-        raise SystemExit("only %d of %d centers" % (len(idx), centers_total))
+    elapsed = 0.0
+    for _ in range(args.steps):
+        store.reset_state()
+        store.sync()
+        if use_dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if use_dist:
+            with torch.cuda.stream(tstream):
+                idx, cdist = sharded.kcenters_sharded(shard, 0, centers_total, 0.0,
+                                                      fresh=True)
+        else:
+            idx, cdist, _ = store.kcenters_run(0, centers_total, 0.0)
+        torch.cuda.synchronize()
+        if use_dist:
+            dist.barrier()
+        elapsed += time.perf_counter() - t0
+        if len(idx) != centers_total:
+            raise SystemExit("only %d of %d centers" % (len(idx), centers_total))
     kern_ms, n_samp = store.timing_end()
     timed_form = store.timing_form()
     ti_report = None
@@ -867,8 +912,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    pairs = float(n_total) * centers_total
-    value = pairs / elapsed
+    # (before anything else runs on the store: the state is the last step's)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, store, idx, cdist, lo, n_local, n_total,
+                     use_dist, rank)
+
+    pairs = float(n_total) * centers_total          # of one step
+    value = pairs * args.steps / elapsed
     bpp = bytes_per_pair(args.atoms)
     # the dominant kernel: the form most of the sampled rounds ran.  A round of
     # 32 candidates is TWO launches of the 16-candidate kernel (candidates 0..15,
@@ -955,13 +1005,13 @@ def main():
         "data": "synthetic",
         "config": {
             "workload": "k-centers RMSD, %d frames x %d atoms, %d centers "
-                        "(BASELINE.json configs[1]), whole fit timed, "
-                        "%d GPU(s)" % (n_total, args.atoms, centers_total,
-                                       world),
+                        "(BASELINE.json configs[1]), one whole fit per "
+                        "step, %d GPU(s)" % (n_total, args.atoms, centers_total,
+                                             world),
             "frames_per_gpu": n_local, "frames_total": n_total,
             "atoms": args.atoms, "centers": centers_total,
-            "centers_per_step": cps,
-            "warmup_centers": warm_centers,
+            "centers_per_step": centers_total,
+            "warmup_centers": centers_total * args.warmup,
             "candidates_per_pass": cands,
             "passes_by_candidates": {str(T): {"passes": p * (2 if T == 32 else 1),
                                               "rounds": p, "centers": k}

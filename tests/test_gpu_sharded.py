@@ -665,7 +665,7 @@ def test_kmedoids_in_mpi_mode(tmp_path, world, backend):
             np.concatenate([p[key + "_d"] for p in parts]), wd)
 
 
-def test_bench_two_ranks_on_one_device():
+def test_bench_two_ranks_on_one_device(tmp_path):
     """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, one
     process per rank), with EK_BENCH_ONE_DEVICE=1: both ranks on device 0 and a
     gloo rendezvous -- the N > 1 code path of the bench (mailboxes over hipIpc,
@@ -680,7 +680,8 @@ def test_bench_two_ranks_on_one_device():
            "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
            "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
            "--warmup", "1", "--frames", "120000", "--atoms", "60", "--centers", "600",
-           "--templates", "600", "--pam-sweeps", "0", "--no-msm", "--no-cpu-baseline"]
+           "--templates", "600", "--pam-sweeps", "0", "--no-msm", "--no-cpu-baseline",
+           "--dump-outputs", str(tmp_path)]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -703,3 +704,15 @@ def test_bench_two_ranks_on_one_device():
         assert sr["chain_with_exchange"] > 0 and sr["plan"] > 0
         assert sum(v["centers"] for v in r["rounds_by_candidates"].values()) == 600
         assert len(r["can_access_peer"]) >= 1
+    # --dump-outputs: the last step's fit, both ranks' blocks gathered on rank 0
+    out = {k: np.load(os.path.join(str(tmp_path), k + ".npy"))
+           for k in ("center_indices", "center_distances", "labels", "distances")}
+    assert out["center_indices"].shape == (600,) and out["center_distances"].shape == (599,)
+    for key, arr in out.items():
+        assert np.all(np.isfinite(arr)), key
+    assert np.all(np.diff(out["center_distances"]) <= 0)     # farthest-point order
+    assert out["labels"].shape == (120000,) and out["distances"].shape == (120000,)
+    assert out["distances"].dtype == np.float32
+    assert len(np.unique(out["center_indices"])) == 600
+    assert out["labels"].min() >= 0 and out["labels"].max() < 600
+    assert np.all(np.isfinite(out["distances"])) and out["distances"].min() >= 0

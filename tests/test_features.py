@@ -22,6 +22,76 @@ def test_oracle_matches_reference_libdist(F):
                                   F["hamming"])
 
 
+def test_oracle_nearest_center_restatement():
+    """oracle.features.assign_to_nearest_center -- one numpy pass per feature
+    over the m x K table -- equals the library's host loop
+    (cluster.util.assign_to_nearest_center: one call per center, strict <)
+    around the oracle callables: ties (the lowest center wins), duplicate
+    centers, +inf distances (label 0 where none is below +inf), NaN distances
+    from +-inf data (never taken), no samples, no centers."""
+    from enspara_amd.cluster import util
+    rng = np.random.RandomState(8)
+    big = rng.normal(size=(60, 5)).astype(np.float32)
+    big[:, 0] *= np.float32(3e19)                   # squares overflow to inf
+    infs = rng.normal(size=(50, 4))
+    infs[rng.rand(50, 4) < 0.2] = np.inf
+    infs[rng.rand(50, 4) < 0.1] = -np.inf           # inf - inf = NaN
+    cases = [
+        (rng.normal(size=(300, 7)).astype(np.float32), (of.euclidean, of.manhattan)),
+        (rng.normal(size=(200, 3)), (of.euclidean, of.manhattan)),
+        (rng.randint(0, 3, size=(400, 4)).astype(np.int64),
+         (of.euclidean, of.manhattan, of.hamming)),
+        (rng.randint(-2, 2, size=(150, 6)).astype(np.int8), (of.hamming,)),
+        (rng.randint(0, 2, size=(150, 3)).astype(np.uint64) * np.uint64(2**63 + 5),
+         (of.hamming,)),
+        (big, (of.euclidean, of.manhattan)),
+        (infs.astype(np.float32), (of.euclidean, of.manhattan)),
+        (infs, (of.euclidean, of.manhattan)),
+    ]
+    for X, metrics in cases:
+        for metric in metrics:
+            for idx in ([0], [5, 5, 17, 3], list(rng.randint(0, len(X), size=40)),
+                        [9, 2, 9, 2]):
+                centers = [X[i] for i in idx]
+                for rows in (X, X[::3], X[:0]):
+                    want = util.assign_to_nearest_center(rows, centers, metric)
+                    got = of.assign_to_nearest_center(rows, centers, metric)
+                    for g, w in zip(got, want):
+                        assert g.dtype == w.dtype
+                        np.testing.assert_array_equal(g, w)
+        # (the cases reach what they are there for)
+        if X is big:
+            assert np.isinf(of.euclidean(X, X[0])).any()
+        if X is infs:
+            assert np.isnan(of.euclidean(X, X[0])).any()
+    got = of.assign_to_nearest_center(X, [], of.euclidean)
+    want = util.assign_to_nearest_center(X, [], of.euclidean)
+    for g, w in zip(got, want):
+        assert g.dtype == w.dtype
+        np.testing.assert_array_equal(g, w)
+    with pytest.raises(ValueError):
+        of.assign_to_nearest_center(X, [X[0]], lambda A, y: of.euclidean(A, y))
+
+
+def test_build_lists_every_included_header():
+    """A header the HIP sources include but build.HEADERS leaves out does not
+    trigger a rebuild when it changes."""
+    import re
+    from enspara_amd import build
+    listed = {os.path.normpath(os.path.join(build.CSRC, h)) for h in build.HEADERS}
+    for h in listed:
+        assert os.path.exists(h), h
+    found = set()
+    for name in sorted(os.listdir(build.CSRC)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        with open(os.path.join(build.CSRC, name)) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M):
+                found.add(os.path.normpath(os.path.join(build.CSRC, inc)))
+    assert "ek_pw.h" in {os.path.basename(h) for h in found}
+    assert found - listed == set(), sorted(found - listed)
+
+
 @pytest.mark.gpu
 def test_device_metrics_match_reference(F):
     from enspara_amd.geometry import libdist
@@ -99,13 +169,13 @@ def test_feature_metric_many_features():
 @pytest.mark.gpu
 def test_resident_feature_kcenters_equals_the_host_loop():
     """kcenters(X, 'euclidean' | 'manhattan') on an array runs the whole loop
-    on the device (ek_feat_kcenters); a wrapped callable of the same metric
-    runs the reference-shaped host loop (kcenters.py:217-231, :243-311).  Same
-    centers, labels, distances -- float32, float64 and integer features (exact
-    ties), count and cut-off stop rules, a warm start, more centers than
-    distinct points."""
+    on the device (ek_feat_kcenters); the ORACLE's callable of the same metric
+    (oracle/features.py, pinned to the reference's compiled module) runs the
+    reference-shaped host loop (kcenters.py:217-231, :243-311).  Same centers,
+    labels, distances -- float32, float64 and integer features (exact ties),
+    count and cut-off stop rules, a warm start, more centers than distinct
+    points."""
     from enspara_amd.cluster.kcenters import kcenters
-    from enspara_amd.geometry import libdist
     rng = np.random.RandomState(5)
     cases = [
         (rng.normal(size=(3001, 17)).astype(np.float32), dict(n_clusters=40)),
@@ -117,8 +187,8 @@ def test_resident_feature_kcenters_equals_the_host_loop():
         (rng.normal(size=(5, 4)), dict(n_clusters=3)),
     ]
     for X, kw in cases:
-        for name, fn in (("euclidean", libdist.euclidean),
-                         ("manhattan", libdist.manhattan)):
+        for name, fn in (("euclidean", of.euclidean),
+                         ("manhattan", of.manhattan)):
             got = kcenters(X, name, **kw)
             want = kcenters(X, lambda A, y, f=fn: f(A, y), **kw)
             assert list(got.center_indices) == list(want.center_indices), name
@@ -130,7 +200,7 @@ def test_resident_feature_kcenters_equals_the_host_loop():
     X = rng.normal(size=(1200, 8)).astype(np.float32)
     init = [X[3], X[700], X[11]]
     got = kcenters(X, "euclidean", n_clusters=15, init_centers=init)
-    want = kcenters(X, lambda A, y: libdist.euclidean(A, y), n_clusters=15,
+    want = kcenters(X, lambda A, y: of.euclidean(A, y), n_clusters=15,
                     init_centers=init)
     assert list(got.center_indices) == list(want.center_indices)
     np.testing.assert_array_equal(got.assignments, want.assignments)
@@ -138,17 +208,21 @@ def test_resident_feature_kcenters_equals_the_host_loop():
 
 
 @pytest.mark.gpu
-def test_resident_feature_pam_equals_the_host_loop():
+def test_resident_feature_pam_equals_the_host_loop(monkeypatch):
     """A PAM sweep over 'euclidean' / 'manhattan' features runs with distances,
     labels and medoids resident on the device (ek_feat_pam_sweep,
-    kmedoids.PAM_FEATURE_DEVICE); with the switch off, the reference-shaped loop
-    (kmedoids.py:575-699) around the device metric.  Same medoids, labels and
+    kmedoids.PAM_FEATURE_DEVICE); the reference-shaped loop (kmedoids.py:575-699)
+    around the ORACLE's callable of the same metric (its nearest-center search
+    in the oracle's vectorised form, pinned on the CPU by
+    test_oracle_nearest_center_restatement).  Same medoids, labels and
     float64 distances, and the caller's RandomState left in the same place --
     float32, float64 and integer features (exact ties in distances and in
     costs), random and explicit proposals, two sweeps, a last chunk of its own
     shape in the cost sums, more features than one LDS chunk."""
     from enspara_amd.cluster import kmedoids as km
+    from enspara_amd.cluster import util
     from enspara_amd.cluster.kcenters import kcenters
+    oracle_metric = {"euclidean": of.euclidean, "manhattan": of.manhattan}
     rng = np.random.RandomState(11)
     cases = [
         (rng.normal(size=(3001, 17)).astype(np.float32), 40),
@@ -166,20 +240,24 @@ def test_resident_feature_pam_equals_the_host_loop():
                 props = None
                 if explicit:
                     props = [int(v) for v in rng.randint(0, len(X), size=K)]
+                assert km._feature_sweep_applies(
+                    X, util._get_distance_method(name), r.distances, props,
+                    r.assignments)
                 out = {}
-                old = km.PAM_FEATURE_DEVICE
-                try:
-                    for dev in (1, 0):
-                        km.PAM_FEATURE_DEVICE = dev
-                        rs = np.random.RandomState(4)
-                        inds = [int(i) for i in r.center_indices]
-                        d, a = r.distances.copy(), r.assignments.copy()
+                for dev in (1, 0):
+                    rs = np.random.RandomState(4)
+                    inds = [int(i) for i in r.center_indices]
+                    d, a = r.distances.copy(), r.assignments.copy()
+                    with monkeypatch.context() as mp:
+                        mp.setattr(km, "PAM_FEATURE_DEVICE", 1)
+                        if not dev:
+                            mp.setattr(util, "assign_to_nearest_center",
+                                       of.assign_to_nearest_center)
                         for _ in range(2):
                             inds, d, a, ctrs = km._kmedoids_pam_update(
-                                X, name, inds, a, d, proposals=props, random_state=rs)
-                        out[dev] = (list(inds), d, a, ctrs, rs.randint(1 << 30, size=3))
-                finally:
-                    km.PAM_FEATURE_DEVICE = old
+                                X, name if dev else oracle_metric[name], inds, a, d,
+                                proposals=props, random_state=rs)
+                    out[dev] = (list(inds), d, a, ctrs, rs.randint(1 << 30, size=3))
                 assert out[1][0] == out[0][0], (name, X.shape, explicit)
                 np.testing.assert_array_equal(out[1][1], out[0][1])
                 np.testing.assert_array_equal(out[1][2], out[0][2])

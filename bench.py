@@ -2,6 +2,7 @@
 """bench.py -- frame x center RMSD pairs/s of the k-centers hot path on MI355X.
 
     python bench.py [--gpus N] [--steps S] [--warmup W] [--dump-outputs DIR]
+                    [--full]
 
 Workload: BASELINE.json configs[1] -- 1,000,000 synthetic frames x 300 atoms,
 5000 centers.  A timed STEP is one WHOLE fit, from the untouched state (every
@@ -42,6 +43,16 @@ one RCCL all-gather per round instead).
 Inputs are resident in HBM (already centred and laid out frame-minor) when the
 timed region starts; generation, upload and layout are reported separately in
 "setup".  Rank 0 prints ONE JSON line.
+
+A plain run does what that line's headline needs and no more: setup, one
+untimed wake-up fit, the W warm-up steps, the S timed steps, the dump, the
+line (`roofline` from the HIP events sampled inside the timed steps).
+--full then measures and checks everything else, after the timed steps and
+the dump: the HBM copy ceiling, a second upload, the one-center roofline
+(`roofline_one_center`), k-hybrid with its oracle parity (`khybrid`), the MSM
+block (`msm`) and the CPU baseline (`cpu_baseline`).  The options that shape
+those legs (--cpu-seconds, --pam-runs, --pam-sweeps N > 0, --msm-frames) are
+refused without --full.
 """
 import argparse
 import hashlib
@@ -75,7 +86,7 @@ def bytes_per_frame_pass(n_atoms, cands):
     return 12 * n_atoms + 20 + 4 * (cands - 1)
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
@@ -108,18 +119,27 @@ def parse():
     p.add_argument("--transport", choices=["mailbox", "gather"], default="mailbox",
                    help="N > 1 / --sharded: a round's exchange through peer "
                         "mailboxes on the device, or one all-gather per round")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, everything else the benchmark "
+                        "measures or checks: the one-center roofline, the HBM "
+                        "copy ceiling, the second upload, k-hybrid (PAM) with "
+                        "its oracle parity, the MSM block and the CPU baseline. "
+                        "The options below up to --pam-sweeps shape these legs")
     p.add_argument("--no-msm", action="store_true",
                    help="skip the MSM block (BASELINE.json configs[4])")
-    p.add_argument("--msm-frames", type=int, default=10_000_000)
-    p.add_argument("--cpu-seconds", type=float, default=15.0,
-                   help="time budget of the CPU baseline leg (rank 0, N=1); 0 = "
+    p.add_argument("--msm-frames", type=int, default=None,
+                   help="frames of assignments of the MSM block (default 10^7)")
+    p.add_argument("--cpu-seconds", type=float, default=None,
+                   help="time budget of the CPU baseline leg (rank 0, N=1; "
+                        "default 15); 0 = "
                         "no budget: the oracle replays ALL centers of the fit "
                         "(labels and distances compared too) and the complete "
                         "PAM sweep -- minutes of CPU work")
     p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--pam-runs", type=int, default=2,
+    p.add_argument("--pam-runs", type=int, default=None,
                    help="repetitions of the PAM measurement, each from the same "
-                        "k-centers result (s_per_sweep is the best, all are listed)")
+                        "k-centers result (s_per_sweep is the best, all are "
+                        "listed; default 2)")
     p.add_argument("--pam-sweeps", type=int, default=None,
                    help="after the timed k-centers region, time this many PAM "
                         "(k-medoids) sweeps over the centers found -- the "
@@ -131,7 +151,25 @@ def parse():
                         "(exercises the RCCL path on a 1-GPU box)")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="write what the last timed step computed to DIR/*.npy")
-    return p.parse_args()
+    args = p.parse_args(argv)
+    if not args.full:
+        # a plain run: setup, warm-up, the timed steps, the dump and the line.
+        # Options that would turn a --full leg on are refused, not ignored.
+        given = [o for o, v in (("--msm-frames", args.msm_frames),
+                                ("--cpu-seconds", args.cpu_seconds),
+                                ("--pam-runs", args.pam_runs)) if v is not None]
+        if args.pam_sweeps:
+            given.append("--pam-sweeps %d" % args.pam_sweeps)
+        if given:
+            p.error("%s: only with --full" % ", ".join(given))
+        args.pam_sweeps, args.no_msm, args.no_cpu_baseline = 0, True, True
+    if args.msm_frames is None:
+        args.msm_frames = 10_000_000
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 15.0
+    if args.pam_runs is None:
+        args.pam_runs = 2
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -208,26 +246,30 @@ def stream_length(args, rank, world):
     return rank * per + args.frames
 
 
-def make_shard(args, lo, count, n_stream):
+def make_shard(args, lo, count, n_stream, threads=1):
     """Frames [lo, lo + count) of the synthetic stream of n_stream frames,
     float32 [count, atoms, 3].  The generator is seeded per 65,536-frame chunk
     and a chunk's draws depend on its length, so every chunk is generated at
     the length it has in the whole stream and then cut: a block is the same
-    data whatever the number of ranks."""
+    data whatever the number of ranks.  The chunks are independent, so
+    `threads` threads generate them at once (numpy leaves the GIL in the bulk
+    of the work); the data do not depend on the number of threads."""
+    from concurrent.futures import ThreadPoolExecutor
     from enspara_amd import synth
     tmpl = synth.templates(args.templates, args.atoms, args.seed)
     out = np.empty((count, args.atoms, 3), dtype=np.float32)
-    c = lo // synth.CHUNK
-    done = 0
-    while done < count:
+
+    def one(c):
         c_lo = c * synth.CHUNK
         c_len = min(synth.CHUNK, n_stream - c_lo)
         chunk = synth.synth_chunk(c, c_len, tmpl, args.seed)
         a = max(lo, c_lo) - c_lo
         b = min(lo + count, c_lo + c_len) - c_lo
-        out[done:done + b - a] = chunk[a:b]
-        done += b - a
-        c += 1
+        out[c_lo + a - lo:c_lo + b - lo] = chunk[a:b]
+
+    chunks = range(lo // synth.CHUNK, (lo + count - 1) // synth.CHUNK + 1)
+    with ThreadPoolExecutor(max(1, min(threads, len(chunks)))) as ex:
+        list(ex.map(one, chunks))
     return out
 
 
@@ -742,13 +784,16 @@ def main():
 
     # ---- setup: synthetic frames -> HBM (centred, frame-minor) ------------
     t0 = time.perf_counter()
+    # (the ranks of one node share its CPUs)
+    synth_threads = max(1, host_threads()[0] //
+                        int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
     if args.data == "walk":
         if world > 1:
             raise SystemExit("--data walk is a one-GPU probe")
         from enspara_amd import synth
         x = synth.walk(n_local, args.atoms, args.seed)
     else:
-        x = make_shard(args, data_lo, n_local, n_stream)
+        x = make_shard(args, data_lo, n_local, n_stream, synth_threads)
     t_gen = time.perf_counter() - t0
     tstream = torch.cuda.Stream(device=local_rank) if use_dist else None
     stream = tstream.cuda_stream if use_dist else None
@@ -757,17 +802,19 @@ def main():
                        global_offset=lo, stream=stream)
     store.sync()
     t_alloc = time.perf_counter() - t0
-    # the frames go up twice: the first load also pins its two host buffers and
-    # allocates the device staging (what a process pays once), the second is the
-    # rate a fit's upload runs at after that
+    # the first load also pins its two host buffers and allocates the device
+    # staging (what a process pays once); with --full the frames go up a second
+    # time, at the rate a fit's upload runs at after that
     t0 = time.perf_counter()
     store.load(x)
     store.sync()
     t_load_first = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    store.load(x)
-    store.sync()
-    t_load = time.perf_counter() - t0
+    t_load = None
+    if args.full:
+        t0 = time.perf_counter()
+        store.load(x)
+        store.sync()
+        t_load = time.perf_counter() - t0
     store.set_frames_per_lane(args.fpl)
     store.set_option("candidates", args.candidates)
     store.set_option("triangle", args.triangle)
@@ -817,8 +864,8 @@ def main():
             idx, _, _ = store.kcenters_run(0, count, 0.0)
         return idx
 
-    # ---- setup, untimed: the GPU has sat idle while the host generated the frames
-    # (~20 s); a throw-away fit brings clocks and caches to their working state
+    # ---- setup, untimed: the GPU has sat idle while the host generated the frames;
+    # a throw-away fit brings clocks and caches to their working state
     # before the W warm-up steps the contract asks for
     t0 = time.perf_counter()
     run(min(centers_total, 2000))
@@ -941,7 +988,6 @@ def main():
     launch_flops = float(n_local) * min(dom, 16) * 18 * args.atoms
     tflops = (launch_flops / (kern_ms * 1e-3)) / 1e12 if kern_ms > 0 else None
     traffic, traffic_src = load_traffic(args, n_local, dom)
-    ceiling = copy_ceiling(min(x.nbytes, 4 << 30), local_rank)
     if dom == 32:
         kernel_name = "ek_pass16_kernel<true, 1> + <true, 2>"
     elif dom == 16:
@@ -953,12 +999,16 @@ def main():
     hbm = {
         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
         "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-        "measured_copy_GBps": ceiling[0],
-        "measured_read_stream_GBps": ceiling[1],
-        "frac_of_measured_read_stream": (achieved / ceiling[1])
-                                        if achieved and ceiling[1] else None,
         "algorithmic_bytes_per_launch": launch_bytes,
     }
+    if args.full:
+        # this GPU's own copy and read-stream rates: runs of their own
+        ceiling = copy_ceiling(min(x.nbytes, 4 << 30), local_rank)
+        hbm.update({
+            "measured_copy_GBps": ceiling[0],
+            "measured_read_stream_GBps": ceiling[1],
+            "frac_of_measured_read_stream": (achieved / ceiling[1])
+                                            if achieved and ceiling[1] else None})
     if dom >= 16:
         roof = {"bound": "mfma", "kernel": kernel_name, "achieved": tflops,
                 "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -1025,6 +1075,7 @@ def main():
             "templates": args.templates if args.data == "templates" else None,
             "data": args.data, "seed": args.seed,
             "world_size": (dist.get_world_size() if use_dist else 1),
+            "full": args.full,
             **({"one_device_check": "EK_BENCH_ONE_DEVICE=1: every rank on device 0, gloo "
                                     "rendezvous -- the N > 1 code path exercised on a "
                                     "one-GPU box, not a measurement"} if one_device else {}),
@@ -1040,11 +1091,12 @@ def main():
                                                mix.items()),
         "triangle_inequality": ti_report,
         "per_rank": per_rank,
-        "setup": {"synth_s": t_gen, "context_and_hbm_allocation_s": t_alloc,
+        "setup": {"synth_s": t_gen, "synth_threads": synth_threads,
+                  "context_and_hbm_allocation_s": t_alloc,
                   "upload_center_layout_s": t_load,
                   "upload_center_layout_first_s": t_load_first,
                   "device_wake_fit_s": t_wake,
-                  "host_to_hbm_GBps": x.nbytes / t_load / 1e9,
+                  "host_to_hbm_GBps": x.nbytes / t_load / 1e9 if t_load else None,
                   "host_to_hbm_first_GBps": x.nbytes / t_load_first / 1e9,
                   "how": "pageable numpy array -> two pinned 256 MiB buffers "
                          "(8 host threads) -> DMA -> centring + three layouts "
@@ -1053,7 +1105,7 @@ def main():
     }
 
     # ---- SURVEY.md 8(d) / BASELINE.md: the one-center pass against HBM ---------
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         out["roofline_one_center"] = one_center_leg(store, args, n_local)
         out["roofline"]["one_center_hbm_frac"] = out["roofline_one_center"]["frac"]
 

@@ -5,7 +5,7 @@ candidates per pass), then one complete PAM sweep of 5000 proposals whose first
 2000 the oracle replays.  The oracle's loops are qcp_oracle.c's (OpenMP): about
 two minutes for the fit and one for the proposals on the GPU box's 16 host
 threads; the COMPLETE replay of the sweep (and of the sweep after it) is
-bench.py --cpu-seconds 0's, kept under profiles/."""
+bench.py --full --cpu-seconds 0's, kept under profiles/."""
 import os
 
 import numpy as np
@@ -71,7 +71,7 @@ def test_pam_sweep_at_the_bench_shape(world):
     medoid for medoid -- and the state the WHOLE sweep leaves is checked on 6000
     sampled frames: every distance is, bit for bit, the RMSD to the medoid the label
     names.  (The complete replay, and the second sweep behind it: bench.py
-    --cpu-seconds 0, profiles/r06/bench_full_parity.json -- five minutes of host
+    --full --cpu-seconds 0, profiles/r06/bench_full_parity.json -- five minutes of host
     time that round 5 spent inside this suite.)"""
     from enspara_amd.cluster import kmedoids as km
     from enspara_amd.device import FrameStore

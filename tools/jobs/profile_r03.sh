@@ -7,7 +7,7 @@ mkdir -p $out
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 has() { [[ " $parts " == *" $1 "* ]]; }
 if has bench; then
-  python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+  python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
   python3 bench.py --candidates 8 --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_candidates8.json 2> /dev/null
   python3 bench.py --candidates 1 --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_candidates1.json 2> /dev/null
   python3 bench.py --sharded --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_sharded_1rank_mailbox.json 2> /dev/null
@@ -15,7 +15,7 @@ if has bench; then
   cut -c1-300 $out/bench_default.json
 fi
 if has trace; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --no-cpu-baseline --pam-sweeps 1 --no-msm > $out/bench_under_rocprof.json 2> $out/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --no-cpu-baseline --pam-sweeps 1 --no-msm > $out/bench_under_rocprof.json 2> $out/trace.err
   f=$(find $out/trace -name "*kernel_trace.csv" | head -1)
   python3 tools/summarize_profile.py trace $f $out/kernel_summary.csv
   cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv 2>/dev/null

@@ -11,7 +11,7 @@ if has tests; then
   tail -3 $out/gpu_tests.log
 fi
 if has bench; then
-  python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+  python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
   python3 bench.py --candidates 32 --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_candidates32.json 2> /dev/null
   python3 bench.py --candidates 8 --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_candidates8.json 2> /dev/null
   python3 bench.py --candidates 1 --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_candidates1.json 2> /dev/null
@@ -22,13 +22,13 @@ fi
 if has full; then
   # the oracle replays ALL 5000 centers (labels and distances compared) and the
   # complete PAM sweep: minutes of CPU work
-  python3 bench.py --cpu-seconds 0 > $out/bench_full_parity.json 2> $out/bench_full_parity.err
+  python3 bench.py --full --cpu-seconds 0 > $out/bench_full_parity.json 2> $out/bench_full_parity.err
   python3 -c "
 import json; d=json.load(open('$out/bench_full_parity.json')); c=d['cpu_baseline']; k=d['khybrid']['parity']
 print('full parity:', c['centers_checked'], c['centers_match_gpu'], c['whole_fit_state_vs_gpu'], k['proposals_replayed_by_oracle'], k['medoids_match_gpu'], k['whole_sweep_state_vs_oracle'])"
 fi
 if has trace; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --no-cpu-baseline --pam-sweeps 1 --no-msm > $out/bench_under_rocprof.json 2> $out/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --no-cpu-baseline --pam-sweeps 1 --no-msm > $out/bench_under_rocprof.json 2> $out/trace.err
   f=$(find $out/trace -name "*kernel_trace.csv" | head -1)
   python3 tools/summarize_profile.py trace $f $out/kernel_summary.csv
   cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv 2>/dev/null

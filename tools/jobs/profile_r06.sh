@@ -13,7 +13,7 @@ if has tests; then
   tail -3 $out/gpu_tests.log
 fi
 if has bench; then
-  python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+  python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
   python3 bench.py --candidates 1 --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_candidates1.json 2> /dev/null
   python3 bench.py --candidates 8 --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_candidates8.json 2> /dev/null
   python3 bench.py --sharded --no-cpu-baseline --pam-sweeps 0 --no-msm > $out/bench_sharded_1rank_mailbox.json 2> /dev/null
@@ -30,10 +30,10 @@ for f in ('candidates1', 'candidates8', 'sharded_1rank_mailbox'):
 PY
 fi
 if has full; then
-  python3 bench.py --cpu-seconds 0 > $out/bench_full_parity.json 2> $out/bench_full_parity.err
+  python3 bench.py --full --cpu-seconds 0 > $out/bench_full_parity.json 2> $out/bench_full_parity.err
 fi
 if has trace; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --no-cpu-baseline --pam-sweeps 1 --no-msm > $out/bench_under_rocprof.json 2> $out/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --no-cpu-baseline --pam-sweeps 1 --no-msm > $out/bench_under_rocprof.json 2> $out/trace.err
   f=$(find $out/trace -name "*kernel_trace.csv" | head -1)
   python3 tools/summarize_profile.py trace $f $out/kernel_summary.csv
   cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv 2>/dev/null
@@ -93,9 +93,10 @@ if has probe; then
   ./tools/probes/split_probe 2>&1 | grep -v amdgpu.ids > $out/split_probe.log; cat $out/split_probe.log
 fi
 if has driver; then
-  # the driver's own command (the kernel sources' hash must match profiles/traffic.json)
+  # the driver's own command, a plain run (the kernel sources' hash must match
+  # profiles/traffic.json; roofline_one_center is a --full leg)
   python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_command.json 2> $out/bench_driver_command.err
-  python3 -c "import json; d = json.load(open('$out/bench_driver_command.json')); print('driver command', d['value'], d['roofline']['frac'], d['roofline'].get('traffic'), d['roofline_one_center'].get('traffic'))"
+  python3 -c "import json; d = json.load(open('$out/bench_driver_command.json')); print('driver command', d['value'], d['roofline']['frac'], d['roofline'].get('traffic'))"
 fi
 if has fuzz; then
   mkdir -p $out/fuzz

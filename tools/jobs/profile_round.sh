@@ -1,14 +1,14 @@
 #!/bin/bash
 # The numbers DESIGN.md / profiles/ quote, from one box and HEAD:
-#   bench_default.json          python3 bench.py                       (the driver's form)
-#   kernel_summary.csv          rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --pam-sweeps 1
+#   bench_default.json          python3 bench.py --full                (every leg of the line)
+#   kernel_summary.csv          rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --pam-sweeps 1
 #   pmc_fetch/write summaries   rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes)
 # usage: profile_round.sh <outdir-under-gpurun_out>
 out=gpurun_out/$1
 mkdir -p $out
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --no-cpu-baseline --pam-sweeps 1 > $out/bench_under_rocprof.json 2> $out/trace.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --no-cpu-baseline --pam-sweeps 1 > $out/bench_under_rocprof.json 2> $out/trace.err
 f=$(find $out/trace -name "*kernel_trace.csv" | head -1)
 python3 tools/summarize_profile.py trace $f $out/kernel_summary.csv
 cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv 2>/dev/null
@@ -30,7 +30,7 @@ grep -E "assign" $out/kernel_summary_assign.csv | cut -c1-110
 grep -E "assign n=" $out/assign.log
 # one pass per center (BASELINE.md's roofline case) and the torch.distributed driver with one rank
 python3 bench.py --candidates 1 --no-cpu-baseline --pam-sweeps 0 > $out/bench_candidates1.json 2> $out/bench_candidates1.err
-python3 bench.py --sharded --no-cpu-baseline --pam-sweeps 1 > $out/bench_sharded_1rank.json 2> $out/bench_sharded_1rank.err
+python3 bench.py --full --sharded --no-cpu-baseline --pam-sweeps 1 > $out/bench_sharded_1rank.json 2> $out/bench_sharded_1rank.err
 # one PAM sweep under the kernel trace (tools/lab_pam.py child): per-kernel table + a window's timeline
 bash tools/jobs/trace_pam.sh $1/pam > /dev/null 2>&1
 python3 tools/lab_pam.py --reps 3 2>&1 | grep -v amdgpu.ids | tail -4 > $out/pam/lab_untraced.log

@@ -55,3 +55,24 @@ class NumpyKrylov:
 
     def combine(self, m, Q):
         return np.asarray(Q).T @ self.V[:m]
+
+
+class NumpyKrylovExpand(NumpyKrylov):
+    """The stand-in with the device's expand(j0, m) as well (ek_krylov_expand):
+    steps j0 .. m-1 back to back, no fresh direction after a breakdown, and a zero
+    vector where the norm was zero.  -> Hessenberg columns [m + 1, m], columns
+    below j0 zero.  NumpyKrylov itself keeps no expand, so that the solver's
+    step-by-step branch stays what the other host tests run."""
+
+    def expand(self, j0, m):
+        H = np.zeros((m + 1, m), order="F")
+        for j in range(j0, m):
+            w = self._apply(self.V[j])
+            for _ in range(2):
+                c = self.V[:j + 1] @ w
+                w = w - c @ self.V[:j + 1]
+                H[:j + 1, j] += c
+            nrm = np.linalg.norm(w)
+            H[j + 1, j] = nrm
+            self.V[j + 1] = w / nrm if nrm > 0 else 0.0
+        return H

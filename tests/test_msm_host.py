@@ -10,24 +10,13 @@ import scipy.sparse
 import scipy.sparse.linalg
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _numpy_krylov import NumpyKrylov  # noqa: E402
+from _numpy_krylov import NumpyKrylov, NumpyKrylovExpand  # noqa: E402
+from _msm_cases import _check_solver_case, _rowstoch  # noqa: E402,F401
 from enspara_amd.msm import transition_matrices as tm  # noqa: E402
 
 
 def _factory(A, m):
     return NumpyKrylov(A, m)
-
-
-def _rowstoch(n, density, seed):
-    rng = np.random.RandomState(seed)
-    C = scipy.sparse.random(n, n, density=density, random_state=rng,
-                            format="csr")
-    C = C + scipy.sparse.diags(np.ones(n)) + \
-        scipy.sparse.diags(np.ones(n - 1) * 0.5, 1) + \
-        scipy.sparse.diags(np.ones(n - 1) * 0.5, -1)
-    C = scipy.sparse.csr_matrix(C)
-    w = np.asarray(C.sum(axis=1)).ravel()
-    return scipy.sparse.diags(1.0 / w) @ C
 
 
 def test_small_dense_all_eigs_matches_reference(golden_dir):
@@ -180,6 +169,19 @@ def test_reducible_matrix_breakdown():
     w = np.sort(np.linalg.eigvals(T.toarray().T).real)[::-1]
     np.testing.assert_allclose(vals, w[:4], atol=1e-9)
     assert abs(vals[1] - 1.0) < 1e-10          # eigenvalue 1 twice
+
+
+@pytest.mark.parametrize("twin", ["steps", "expand"])
+@pytest.mark.parametrize("case", ["four_cycles", "rank_one", "kron", 257, 1000, 1001])
+def test_solver_through_both_branches_of_expand(case, twin):
+    """transition_matrices._expand has two branches: single steps (a space without
+    expand: NumpyKrylov) and one expand call whose tail is redone with steps from the
+    first tiny sub-diagonal entry (the device; NumpyKrylovExpand here).  Both, on
+    matrices that really break down -- a fresh direction through step(apply=False)
+    is counted, which test_reducible_matrix_breakdown's matrix never asks for: there
+    rounding noise supplies one before the 1e-13 test fires -- and at the sizes round
+    the full-basis limit of 1000 states."""
+    _check_solver_case(case, NumpyKrylov if twin == "steps" else NumpyKrylovExpand)
 
 
 def _metastable(n_blocks, size, eps, seed):

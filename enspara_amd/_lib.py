@@ -50,6 +50,9 @@ SYMBOLS = [
     "ek_krylov_combine", "ek_krylov_expand", "ek_krylov_set_filter",
     "ek_feat_create", "ek_feat_destroy", "ek_feat_load", "ek_feat_distance",
     "ek_feat_kcenters", "ek_feat_pam_sweep", "ek_feat_pam_release",
+    "ek_feat_record_bytes", "ek_feat_create_sharded", "ek_feat_state_reset",
+    "ek_feat_state_upload", "ek_feat_state_download", "ek_feat_local_candidate",
+    "ek_feat_kcenters_step", "ek_feat_history_download", "ek_feat_history_reset",
     "ek_set_frames_per_lane", "ek_set_option", "ek_get_option", "ek_last_run_timing",
     "ek_reserve_centers",
     "ek_debug_guards",
@@ -223,6 +226,17 @@ def load():
     L.ek_feat_pam_release.restype = None
     L.ek_feat_kcenters.argtypes = [vp, i32, i32, i32, C.c_double, f64p, i32p, i64p,
                                    i32p, f64p]
+    L.ek_feat_record_bytes.restype = C.c_size_t
+    L.ek_feat_record_bytes.argtypes = [i32, i32]
+    L.ek_feat_create_sharded.argtypes = [C.c_int, i64, i32, i32, i64, vp,
+                                         C.POINTER(vp)]
+    L.ek_feat_state_reset.argtypes = [vp]
+    L.ek_feat_state_upload.argtypes = [vp, f64p, i32p]
+    L.ek_feat_state_download.argtypes = [vp, f64p, i32p]
+    L.ek_feat_local_candidate.argtypes = [vp, vp]
+    L.ek_feat_kcenters_step.argtypes = [vp, i32, vp, i32, i32, C.c_double, vp]
+    L.ek_feat_history_download.argtypes = [vp, i32, i32, i64p, f64p, i32p]
+    L.ek_feat_history_reset.argtypes = [vp]
     L.ek_set_frames_per_lane.argtypes = [vp, C.c_int]
     L.ek_set_option.argtypes = [vp, i32, i32]
     L.ek_get_option.argtypes = [vp, i32, i32p]

@@ -58,6 +58,11 @@ def hybrid(X, distance_method, n_iters=5, n_clusters=np.inf, dist_cutoff=0,
     """reference hybrid.py:112-162"""
     distance_method = util._get_distance_method(distance_method)
     if not util.is_device_rmsd(distance_method):
+        if mpi_mode:
+            raise ImproperlyConfigured(
+                "KHybrid in MPI mode runs metric 'rmsd' on the device; there is "
+                "no sharded PAM sweep for a feature or callable metric "
+                "(KCenters has an mpi_mode for 'euclidean' / 'manhattan')")
         result = _kc.kcenters(
             X, distance_method, n_clusters=n_clusters, dist_cutoff=dist_cutoff,
             init_centers=init_centers,

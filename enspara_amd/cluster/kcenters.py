@@ -43,7 +43,8 @@ class KCenters(BaseEstimator, ClusterMixin, util.MolecularClusterMixin):
     ``random_first_center`` (not implemented there either),
     ``random_state``, ``mpi_mode`` (None: True when the torch.distributed group
     has more than one rank, as the reference's ``mpi.size() != 1``,
-    kcenters.py:73; every rank then passes its own frames, see
+    kcenters.py:73; every rank then passes its own frames -- or, for
+    'euclidean' / 'manhattan' / libdist.hamming, its own 2-D samples --, see
     :mod:`enspara_amd.sharded`).  ``device`` selects the GPU.
     """
 
@@ -99,13 +100,25 @@ def kcenters(traj, distance_method, n_clusters=np.inf, dist_cutoff=0,
         raise NotImplementedError(
             "We haven't implemented kcenters 'random_first_center' yet.")
     if mpi_mode:
-        # every rank of the torch.distributed group passes its own frames
-        # (kcenters.py:314-378); RMSD only
-        if not util.is_device_rmsd(distance_method):
-            raise ImproperlyConfigured(
-                "mpi_mode is available for metric 'rmsd' "
-                "(one process per GPU over torch.distributed)")
+        # every rank of the torch.distributed group passes its own frames /
+        # samples (kcenters.py:314-378)
         from .. import sharded
+        if not util.is_device_rmsd(distance_method):
+            mid = getattr(distance_method, "device_metric_id", None)
+            if mid is None:
+                raise ImproperlyConfigured(
+                    "mpi_mode is available for metric 'rmsd' and the device "
+                    "feature metrics ('euclidean', 'manhattan', "
+                    "libdist.hamming); there is no host loop across ranks for "
+                    "a callable metric")
+            if use_triangle_inequality:
+                raise ImproperlyConfigured(
+                    "use_triangle_inequality has no sharded form for a feature "
+                    "metric (the single-process run keeps the host loop for "
+                    "it): mpi_mode cannot honour it")
+            return sharded.fit_features_sharded(
+                traj, mid, n_clusters=n_clusters, dist_cutoff=dist_cutoff,
+                init_centers=init_centers)
         return sharded.fit_sharded(
             traj, n_clusters=n_clusters, dist_cutoff=dist_cutoff, n_iters=0,
             use_triangle_inequality=use_triangle_inequality,

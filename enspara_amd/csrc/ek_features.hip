@@ -58,6 +58,13 @@ struct ek_feat {
     int64_t *hist = nullptr;
     int32_t hist_cap = 0;
     FeatPam *pam = nullptr;
+    // one shard of a k-centers run over several handles (ek_feat_kcenters_step)
+    bool own_stream = true;   // false: s is the caller's (ek_feat_create_sharded)
+    int64_t goff = 0;         // global index of local sample 0
+    struct FeatShardCtl *sctl = nullptr;
+    int64_t *shist_idx = nullptr;   // [shist_cap] winners' global indices
+    double *shist_d = nullptr;      // ... and their distances before the update
+    int32_t shist_cap = 0;
 };
 
 // per-workgroup partial of the arg-max over float64 distances
@@ -209,17 +216,24 @@ extern "C" int ek_feat_destroy(ek_feat *k)
     (void)hipFree(k->bm);
     (void)hipFree(k->ctl);
     (void)hipFree(k->hist);
-    if (k->s)
+    (void)hipFree(k->sctl);
+    (void)hipFree(k->shist_idx);
+    (void)hipFree(k->shist_d);
+    if (k->s && k->own_stream)
         (void)hipStreamDestroy(k->s);
     delete k;
     return EK_OK;
 }
 
-extern "C" int ek_feat_create(int device, int64_t n_samples, int32_t n_features,
-                              int32_t elem_kind, ek_feat **out)
+// (global_offset, stream: a shard of a larger sample set on the caller's stream;
+// stream == NULL: a stream of the handle's own)
+extern "C" int ek_feat_create_sharded(int device, int64_t n_samples,
+                                      int32_t n_features, int32_t elem_kind,
+                                      int64_t global_offset, void *stream,
+                                      ek_feat **out)
 {
     if (!out || n_samples < 0 || n_features < 1 || elem_kind < 0 ||
-        elem_kind > 2)
+        elem_kind > 2 || global_offset < 0)
         return ek_set_error(EK_EARG, "ek_feat_create: bad argument");
     *out = nullptr;
     FE_HIP(hipSetDevice(device));
@@ -232,9 +246,16 @@ extern "C" int ek_feat_create(int device, int64_t n_samples, int32_t n_features,
     k->kind = elem_kind;
     k->esize = elem_kind == 0 ? 4 : 8;
     k->n_tiles = (n_samples + EK_TILE - 1) / EK_TILE;
+    k->goff = global_offset;
     const size_t tb = (size_t)std::max<int64_t>(k->n_tiles, 1) * n_features *
                       EK_TILE * k->esize;
-    hipError_t e = hipStreamCreateWithFlags(&k->s, hipStreamNonBlocking);
+    hipError_t e = hipSuccess;
+    if (stream) {
+        k->s = (hipStream_t)stream;
+        k->own_stream = false;
+    } else {
+        e = hipStreamCreateWithFlags(&k->s, hipStreamNonBlocking);
+    }
     if (e == hipSuccess)
         e = hipMalloc(&k->tiles, tb);
     if (e == hipSuccess)
@@ -251,6 +272,13 @@ extern "C" int ek_feat_create(int device, int64_t n_samples, int32_t n_features,
     }
     *out = k;
     return EK_OK;
+}
+
+extern "C" int ek_feat_create(int device, int64_t n_samples, int32_t n_features,
+                              int32_t elem_kind, ek_feat **out)
+{
+    return ek_feat_create_sharded(device, n_samples, n_features, elem_kind, 0,
+                                  nullptr, out);
 }
 
 extern "C" int ek_feat_load(ek_feat *k, const void *X, int64_t first,
@@ -624,6 +652,418 @@ extern "C" int ek_feat_kcenters(ek_feat *k, int32_t metric, int32_t first_label,
                               hipMemcpyDeviceToHost, k->s));
         FE_HIP(hipStreamSynchronize(k->s));
     }
+    return EK_OK;
+}
+
+// ===========================================================================
+// k-centers in feature space over several shards (one ek_feat handle each)
+// ===========================================================================
+// Reference: the MPI iteration of enspara/cluster/kcenters.py:314-378 for any
+// metric -- two allgathers (:332-335), the owner's arg-max (:337), a broadcast
+// of the new center and the stop test (:217).  Here every shard keeps ONE
+// candidate record
+//   { double max_dist; int64 global_index; T row[F] }      (16-byte multiple)
+// -- the maximum of its float64 distances, global_offset + the first local index
+// of that maximum, that sample's features -- and the caller exchanges the records
+// (one all-gather).  The step is one launch per center and shard: every
+// workgroup picks the winner among the records (largest max_dist, lowest record
+// index among equal ones: with contiguous shards in rank order np.argmax's first
+// index over the concatenated data, :282 / :337), applies the stop rule
+// `!(max > cutoff)` to it, computes metric(X_local, winner's row) with the
+// arithmetic of feat_distance_kernel, applies the strict-< update and leaves its
+// (max, first index) partial; the workgroup that arrives last (ek_arrive_last_tree:
+// the partials cross workgroups as agent-scope relaxed atomics) reduces them and
+// writes the shard's next record, row gathered from the tiles.  A shard without
+// samples writes max_dist = -inf: it never wins.
+struct FeatShardCtl {
+    int32_t n_done;       // labels applied so far (last label + 1)
+    int32_t stopped;      // a step found max <= cutoff: later steps return at once
+    // arrival counters of the launch in flight (ek_arrive_last_tree: a million
+    // samples are 3907 workgroups, and as many returning atomics on one address
+    // serialise -- measured, they nearly doubled the step's time)
+    unsigned int top;
+    unsigned int pad;
+    unsigned int leaves[EK_ARRIVE_G];
+};
+
+extern "C" size_t ek_feat_record_bytes(int32_t n_features, int32_t elem_kind)
+{
+    if (n_features < 1 || elem_kind < 0 || elem_kind > 2)
+        return 0;
+    const size_t b = 16 + (size_t)n_features * (elem_kind == 0 ? 4 : 8);
+    return (b + 15) / 16 * 16;
+}
+
+// the block's best (value, index) pair, in every thread; rv / ri: one slot per wave
+__device__ __forceinline__ void feat_block_argmax_all(double &v, int64_t &i, double *rv,
+                                                      int64_t *ri)
+{
+    feat_wave_argmax(v, i);
+    __syncthreads();                    // (rv / ri may still be read from a call before)
+    if ((threadIdx.x & (EK_WAVE - 1)) == 0) {
+        rv[threadIdx.x / EK_WAVE] = v;
+        ri[threadIdx.x / EK_WAVE] = i;
+    }
+    __syncthreads();
+    v = rv[0];
+    i = ri[0];
+#pragma unroll
+    for (int w = 1; w < EK_BLOCK / EK_WAVE; ++w)
+        if (feat_better(rv[w], ri[w], v, i)) {
+            v = rv[w];
+            i = ri[w];
+        }
+}
+
+// Every workgroup hands in its (max, first local index) partial; the one that
+// arrives last reduces all of them and writes the shard's record.  True in all
+// threads of that workgroup.
+template <typename T>
+__device__ __forceinline__ bool feat_shard_finish(double v, int64_t i, double *rv,
+                                                  int64_t *ri, const T *__restrict__ tiles,
+                                                  int64_t n, int F, int64_t goff,
+                                                  FeatBlockMax *bm, FeatShardCtl *ctl,
+                                                  unsigned char *own_rec)
+{
+    feat_block_argmax_all(v, i, rv, ri);
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&bm[blockIdx.x].val, v, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&bm[blockIdx.x].idx, i, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!ek_arrive_last_tree(&ctl->top, ctl->leaves))
+        return false;
+    v = -__builtin_inf();
+    i = 0x7fffffffffffffffLL;
+    for (unsigned int b = threadIdx.x; b < gridDim.x; b += EK_BLOCK) {
+        const double ov = __hip_atomic_load(&bm[b].val, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+        const int64_t oi = __hip_atomic_load(&bm[b].idx, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+        if (feat_better(ov, oi, v, i)) {
+            v = ov;
+            i = oi;
+        }
+    }
+    feat_block_argmax_all(v, i, rv, ri);
+    const bool any = i < n;             // (no sample: v = -inf, no row)
+    T *row = (T *)(own_rec + 16);
+    const T *p = tiles + (any ? (size_t)(i / EK_TILE) * (size_t)F * EK_TILE + (i % EK_TILE)
+                              : (size_t)0);
+    for (int j = threadIdx.x; j < F; j += EK_BLOCK)
+        row[j] = any ? p[(size_t)j * EK_TILE] : (T)0;
+    if (threadIdx.x == 0) {
+        *(double *)own_rec = any ? v : -__builtin_inf();
+        *(int64_t *)(own_rec + 8) = any ? goff + i : (int64_t)-1;
+    }
+    return true;
+}
+
+// the record of the state as it stands (before the first step, after a reset or
+// a warm start)
+template <typename T>
+__global__ void __launch_bounds__(EK_BLOCK)
+feat_shard_candidate_kernel(const T *__restrict__ tiles, int64_t n, int F, int64_t goff,
+                            const double *__restrict__ dist, FeatBlockMax *bm,
+                            FeatShardCtl *ctl, unsigned char *own_rec)
+{
+    __shared__ double rv[EK_BLOCK / EK_WAVE];
+    __shared__ int64_t ri[EK_BLOCK / EK_WAVE];
+    const int64_t f = (int64_t)blockIdx.x * EK_BLOCK + threadIdx.x;
+    double v = -__builtin_inf();
+    int64_t i = 0x7fffffffffffffffLL;
+    if (f < n) {
+        v = dist[f];
+        i = f;
+    }
+    feat_shard_finish<T>(v, i, rv, ri, tiles, n, F, goff, bm, ctl, own_rec);
+}
+
+// (recs and own_rec may be the same memory -- one shard, no exchange --: the last
+// workgroup writes own_rec only after every workgroup has read what it needs)
+template <typename T, int METRIC>
+__global__ void __launch_bounds__(EK_BLOCK)
+feat_shard_step_kernel(const T *__restrict__ tiles, int64_t n, int F, int64_t goff,
+                       const unsigned char *recs, int n_recs, size_t rec_bytes,
+                       int32_t label, double cutoff, double *__restrict__ dist,
+                       int32_t *__restrict__ assign, FeatBlockMax *bm, FeatShardCtl *ctl,
+                       int64_t *__restrict__ hist_idx, double *__restrict__ hist_d,
+                       unsigned char *own_rec)
+{
+    __shared__ T ys[FY_CHUNK];
+    __shared__ double rv[EK_BLOCK / EK_WAVE];
+    __shared__ int64_t ri[EK_BLOCK / EK_WAVE];
+    if (ctl->stopped)
+        return;
+    // the winner among the records: the same in every workgroup of every shard
+    double wv = -__builtin_inf();
+    int64_t wr = 0x7fffffffffffffffLL;
+    for (int r = threadIdx.x; r < n_recs; r += EK_BLOCK) {
+        const double v = *(const double *)(recs + (size_t)r * rec_bytes);
+        if (feat_better(v, r, wv, wr)) {
+            wv = v;
+            wr = r;
+        }
+    }
+    feat_block_argmax_all(wv, wr, rv, ri);
+    if (!(wv > cutoff)) {               // kcenters.py:217 (also: no record holds a sample)
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            ctl->stopped = 1;
+        return;
+    }
+    const unsigned char *win = recs + (size_t)wr * rec_bytes;
+    const int64_t win_gidx = *(const int64_t *)(win + 8);
+    const T *y = (const T *)(win + 16);
+    const int64_t f = (int64_t)blockIdx.x * EK_BLOCK + threadIdx.x;
+    const T *p = tiles + (size_t)(f / EK_TILE) * (size_t)F * EK_TILE + (f % EK_TILE);
+    double acc = 0.0;
+    for (int j0 = 0; j0 < F; j0 += FY_CHUNK) {
+        const int w = (F - j0 < FY_CHUNK) ? (F - j0) : FY_CHUNK;
+        __syncthreads();
+        for (int j = threadIdx.x; j < w; j += EK_BLOCK)
+            ys[j] = y[j0 + j];
+        __syncthreads();
+#pragma unroll 8
+        for (int j = 0; j < w; ++j)
+            FeatAcc<T, METRIC>::add(acc, __builtin_nontemporal_load(
+                                             p + (size_t)(j0 + j) * EK_TILE),
+                                    ys[j]);
+    }
+    double v = -__builtin_inf();
+    int64_t i = 0x7fffffffffffffffLL;
+    if (f < n) {
+        acc = feat_finish<METRIC>(acc, F);
+        double cur = dist[f];
+        if (acc < cur) {                    // kcenters.py:304: strict <
+            cur = acc;
+            dist[f] = acc;
+            assign[f] = label;
+        }
+        v = cur;
+        i = f;
+    }
+    if (feat_shard_finish<T>(v, i, rv, ri, tiles, n, F, goff, bm, ctl, own_rec) &&
+        threadIdx.x == 0) {
+        hist_idx[label] = win_gidx;
+        hist_d[label] = wv;
+        ctl->n_done = label + 1;
+    }
+}
+
+static int feat_shard_alloc(ek_feat *k, int32_t label)
+{
+    const int nb = (int)std::max<int64_t>((k->n + EK_BLOCK - 1) / EK_BLOCK, 1);
+    if (!k->kdist) {
+        const size_t n1 = (size_t)std::max<int64_t>(k->n, 1);
+        FE_HIP(hipMalloc((void **)&k->kdist, n1 * sizeof(double)));
+        FE_HIP(hipMalloc((void **)&k->kassign, n1 * sizeof(int32_t)));
+        FE_HIP(hipMalloc((void **)&k->bm, (size_t)nb * sizeof(FeatBlockMax)));
+        FE_HIP(hipMalloc((void **)&k->ctl, sizeof(FeatCtl)));
+    }
+    if (!k->sctl) {
+        FE_HIP(hipMalloc((void **)&k->sctl, sizeof(FeatShardCtl)));
+        FE_HIP(hipMemsetAsync(k->sctl, 0, sizeof(FeatShardCtl), k->s));
+    }
+    if (label >= k->shist_cap) {
+        int32_t cap = std::max(k->shist_cap, 1024);
+        while (cap <= label)
+            cap *= 2;
+        int64_t *hi = nullptr;
+        double *hd = nullptr;
+        FE_HIP(hipMalloc((void **)&hi, (size_t)cap * sizeof(int64_t)));
+        FE_HIP(hipMalloc((void **)&hd, (size_t)cap * sizeof(double)));
+        FE_HIP(hipMemsetAsync(hi, 0xff, (size_t)cap * sizeof(int64_t), k->s));
+        FE_HIP(hipMemsetAsync(hd, 0, (size_t)cap * sizeof(double), k->s));
+        if (k->shist_cap) {
+            FE_HIP(hipMemcpyAsync(hi, k->shist_idx, (size_t)k->shist_cap * sizeof(int64_t),
+                                  hipMemcpyDeviceToDevice, k->s));
+            FE_HIP(hipMemcpyAsync(hd, k->shist_d, (size_t)k->shist_cap * sizeof(double),
+                                  hipMemcpyDeviceToDevice, k->s));
+        }
+        FE_HIP(hipStreamSynchronize(k->s));
+        (void)hipFree(k->shist_idx);
+        (void)hipFree(k->shist_d);
+        k->shist_idx = hi;
+        k->shist_d = hd;
+        k->shist_cap = cap;
+    }
+    return EK_OK;
+}
+
+__global__ void __launch_bounds__(EK_BLOCK)
+feat_fill_state_kernel(double *__restrict__ dist, int32_t *__restrict__ assign, int64_t n)
+{
+    const int64_t f = (int64_t)blockIdx.x * EK_BLOCK + threadIdx.x;
+    if (f < n) {
+        dist[f] = __builtin_inf();
+        assign[f] = -1;
+    }
+}
+
+extern "C" int ek_feat_history_reset(ek_feat *k)
+{
+    if (!k)
+        return ek_set_error(EK_EARG, "ek_feat_history_reset: NULL handle");
+    FE_HIP(hipSetDevice(k->device));
+    int rc = feat_shard_alloc(k, 0);
+    if (rc)
+        return rc;
+    FE_HIP(hipMemsetAsync(k->shist_idx, 0xff, (size_t)k->shist_cap * sizeof(int64_t), k->s));
+    FE_HIP(hipMemsetAsync(k->shist_d, 0, (size_t)k->shist_cap * sizeof(double), k->s));
+    FE_HIP(hipMemsetAsync(k->sctl, 0, sizeof(FeatShardCtl), k->s));
+    return EK_OK;
+}
+
+extern "C" int ek_feat_state_reset(ek_feat *k)
+{
+    if (!k)
+        return ek_set_error(EK_EARG, "ek_feat_state_reset: NULL handle");
+    FE_HIP(hipSetDevice(k->device));
+    int rc = feat_shard_alloc(k, 0);
+    if (rc)
+        return rc;
+    if (k->n > 0) {
+        hipLaunchKernelGGL(feat_fill_state_kernel,
+                           dim3((unsigned)((k->n + EK_BLOCK - 1) / EK_BLOCK)), dim3(EK_BLOCK),
+                           0, k->s, k->kdist, k->kassign, k->n);
+        FE_HIP(hipGetLastError());
+    }
+    return ek_feat_history_reset(k);
+}
+
+extern "C" int ek_feat_state_upload(ek_feat *k, const double *dist_host,
+                                    const int32_t *assign_host)
+{
+    if (!k || ((!dist_host || !assign_host) && k->n > 0))
+        return ek_set_error(EK_EARG, "ek_feat_state_upload: NULL argument");
+    FE_HIP(hipSetDevice(k->device));
+    int rc = feat_shard_alloc(k, 0);
+    if (rc)
+        return rc;
+    if (k->n > 0) {
+        FE_HIP(hipMemcpyAsync(k->kdist, dist_host, (size_t)k->n * sizeof(double),
+                              hipMemcpyHostToDevice, k->s));
+        FE_HIP(hipMemcpyAsync(k->kassign, assign_host, (size_t)k->n * sizeof(int32_t),
+                              hipMemcpyHostToDevice, k->s));
+    }
+    FE_HIP(hipStreamSynchronize(k->s));
+    return EK_OK;
+}
+
+extern "C" int ek_feat_state_download(ek_feat *k, double *dist_host, int32_t *assign_host)
+{
+    if (!k)
+        return ek_set_error(EK_EARG, "ek_feat_state_download: NULL handle");
+    if (!k->kdist)
+        return ek_set_error(EK_ESTATE, "ek_feat_state_download: no state on the device");
+    FE_HIP(hipSetDevice(k->device));
+    if (dist_host && k->n > 0)
+        FE_HIP(hipMemcpyAsync(dist_host, k->kdist, (size_t)k->n * sizeof(double),
+                              hipMemcpyDeviceToHost, k->s));
+    if (assign_host && k->n > 0)
+        FE_HIP(hipMemcpyAsync(assign_host, k->kassign, (size_t)k->n * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, k->s));
+    FE_HIP(hipStreamSynchronize(k->s));
+    return EK_OK;
+}
+
+extern "C" int ek_feat_local_candidate(ek_feat *k, void *rec_dev)
+{
+    if (!k || !rec_dev)
+        return ek_set_error(EK_EARG, "ek_feat_local_candidate: NULL argument");
+    if (!k->loaded || !k->kdist)
+        return ek_set_error(EK_ESTATE, "ek_feat_local_candidate: samples and a state "
+                                       "(ek_feat_state_reset / _upload) first");
+    FE_HIP(hipSetDevice(k->device));
+    int rc = feat_shard_alloc(k, 0);
+    if (rc)
+        return rc;
+    const unsigned blocks = (unsigned)std::max<int64_t>((k->n + EK_BLOCK - 1) / EK_BLOCK, 1);
+    if (k->esize == 4)
+        hipLaunchKernelGGL(feat_shard_candidate_kernel<float>, dim3(blocks), dim3(EK_BLOCK),
+                           0, k->s, (const float *)k->tiles, k->n, k->F, k->goff, k->kdist,
+                           k->bm, k->sctl, (unsigned char *)rec_dev);
+    else
+        hipLaunchKernelGGL(feat_shard_candidate_kernel<double>, dim3(blocks), dim3(EK_BLOCK),
+                           0, k->s, (const double *)k->tiles, k->n, k->F, k->goff, k->kdist,
+                           k->bm, k->sctl, (unsigned char *)rec_dev);
+    FE_HIP(hipGetLastError());
+    return EK_OK;
+}
+
+extern "C" int ek_feat_kcenters_step(ek_feat *k, int32_t metric, const void *all_recs_dev,
+                                     int32_t n_recs, int32_t label, double dist_cutoff,
+                                     void *own_rec_dev)
+{
+    if (!k || !all_recs_dev || !own_rec_dev || metric < 0 || metric > 2 || n_recs < 1 ||
+        label < 0)
+        return ek_set_error(EK_EARG, "ek_feat_kcenters_step: bad argument");
+    if (!k->loaded || !k->kdist)
+        return ek_set_error(EK_ESTATE, "ek_feat_kcenters_step: samples and a state "
+                                       "(ek_feat_state_reset / _upload) first");
+    if ((metric == 2) != (k->kind == 2))
+        return ek_set_error(EK_EARG, "ek_feat_kcenters_step: hamming needs integer "
+                                     "samples, the other metrics floating point");
+    FE_HIP(hipSetDevice(k->device));
+    int rc = feat_shard_alloc(k, label);
+    if (rc)
+        return rc;
+    const unsigned blocks = (unsigned)std::max<int64_t>((k->n + EK_BLOCK - 1) / EK_BLOCK, 1);
+    const size_t rb = ek_feat_record_bytes(k->F, k->kind);
+#define FS_STEP(T, M)                                                          \
+    hipLaunchKernelGGL((feat_shard_step_kernel<T, M>), dim3(blocks),           \
+                       dim3(EK_BLOCK), 0, k->s, (const T *)k->tiles, k->n,     \
+                       k->F, k->goff, (const unsigned char *)all_recs_dev,     \
+                       (int)n_recs, rb, label, dist_cutoff, k->kdist,          \
+                       k->kassign, k->bm, k->sctl, k->shist_idx, k->shist_d,   \
+                       (unsigned char *)own_rec_dev)
+    if (metric == 2)
+        FS_STEP(long long, 2);
+    else if (k->kind == 0) {
+        if (metric == 0)
+            FS_STEP(float, 0);
+        else
+            FS_STEP(float, 1);
+    } else {
+        if (metric == 0)
+            FS_STEP(double, 0);
+        else
+            FS_STEP(double, 1);
+    }
+#undef FS_STEP
+    FE_HIP(hipGetLastError());
+    return EK_OK;
+}
+
+extern "C" int ek_feat_history_download(ek_feat *k, int32_t first, int32_t count,
+                                        int64_t *center_index_out, double *center_dist_out,
+                                        int32_t *n_done)
+{
+    if (!k || first < 0 || count < 0)
+        return ek_set_error(EK_EARG, "ek_feat_history_download: bad argument");
+    FE_HIP(hipSetDevice(k->device));
+    int rc = feat_shard_alloc(k, 0);
+    if (rc)
+        return rc;
+    FeatShardCtl ctl;
+    FE_HIP(hipMemcpyAsync(&ctl, k->sctl, sizeof(ctl), hipMemcpyDeviceToHost, k->s));
+    const int32_t avail = std::max(0, std::min(count, k->shist_cap - first));
+    if (avail > 0 && center_index_out)
+        FE_HIP(hipMemcpyAsync(center_index_out, k->shist_idx + first,
+                              (size_t)avail * sizeof(int64_t), hipMemcpyDeviceToHost, k->s));
+    if (avail > 0 && center_dist_out)
+        FE_HIP(hipMemcpyAsync(center_dist_out, k->shist_d + first,
+                              (size_t)avail * sizeof(double), hipMemcpyDeviceToHost, k->s));
+    FE_HIP(hipStreamSynchronize(k->s));
+    for (int32_t i = avail; i < count; ++i) {
+        if (center_index_out)
+            center_index_out[i] = -1;
+        if (center_dist_out)
+            center_dist_out[i] = 0.0;
+    }
+    if (n_done)
+        *n_done = ctl.n_done;
     return EK_OK;
 }
 

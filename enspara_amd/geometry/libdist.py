@@ -102,6 +102,104 @@ class _Resident:
             pass
 
 
+class FeatureStore(_Resident):
+    """One shard of a sample set on the device for the k-centers loop over
+    several shards (ek_feat_create_sharded, ek_feat_kcenters_step): this
+    handle's samples are [global_offset, global_offset + n) of the whole set,
+    its float64 distances and int32 labels stay on the device.  ``stream``: a
+    hipStream_t handle (e.g. ``torch.cuda.Stream().cuda_stream``) the launches
+    go to, so that a caller's collectives on that stream are ordered with them;
+    0 / None: a stream of the handle's own.  Counterpart of
+    :class:`enspara_amd.device.FrameStore` for feature metrics."""
+
+    def __init__(self, Xc, kind, device=0, global_offset=0, stream=None):
+        self.L = _lib.load()
+        self.kind = int(kind)
+        self.device = int(device)
+        self.n, self.F = int(Xc.shape[0]), int(Xc.shape[1])
+        self.global_offset = int(global_offset)
+        h = C.c_void_p()
+        _lib.check(self.L.ek_feat_create_sharded(
+            self.device, self.n, self.F, self.kind, self.global_offset,
+            C.c_void_p(int(stream) if stream else None), C.byref(h)))
+        self._h = h
+        _lib.check(self.L.ek_feat_load(
+            self._h, Xc.ctypes.data_as(C.c_void_p) if self.n else None, 0,
+            self.n))
+        self.record_bytes = int(self.L.ek_feat_record_bytes(self.F, self.kind))
+        self.dtype = Xc.dtype
+
+    def distance(self, metric, y, out):
+        """metric(X_local, y) into ``out`` (float64 [n]); y in any dtype"""
+        y = np.ascontiguousarray(y, dtype=self.dtype)
+        if y.shape != (self.F,):
+            raise DataInvalid("Target data point dimension (%s) must match data "
+                              "array dimension (%s)" % (y.shape, self.F))
+        if self.n:
+            super().distance(metric, y, out)
+
+    @classmethod
+    def from_array(cls, X, metric, device=0, global_offset=0, stream=None):
+        """X in the dtype ``metric`` (0 euclidean, 1 manhattan, 2 hamming)
+        computes in: float32 stays, int64 for hamming, float64 otherwise"""
+        Xa = np.asarray(X)
+        dt = _working_dtype(Xa, metric == 2)
+        return cls(np.ascontiguousarray(Xa, dtype=dt), _KIND[np.dtype(dt).name],
+                   device, global_offset, stream)
+
+    def reset_state(self):
+        _lib.check(self.L.ek_feat_state_reset(self._h))
+
+    def upload_state(self, distances, assignments):
+        d = np.ascontiguousarray(distances, dtype=np.float64)
+        a = np.ascontiguousarray(assignments, dtype=np.int32)
+        if len(d) != self.n or len(a) != self.n:
+            raise DataInvalid("state of %d / %d entries for %d samples"
+                              % (len(d), len(a), self.n))
+        _lib.check(self.L.ek_feat_state_upload(self._h, _lib.f64p(d),
+                                               _lib.i32p(a)))
+
+    def download_state(self):
+        """-> (distances float64 [n], labels int32 [n]) on the host"""
+        d = np.empty(self.n, dtype=np.float64)
+        a = np.empty(self.n, dtype=np.int32)
+        _lib.check(self.L.ek_feat_state_download(self._h, _lib.f64p(d),
+                                                 _lib.i32p(a)))
+        return d, a
+
+    def local_candidate(self, rec_ptr):
+        _lib.check(self.L.ek_feat_local_candidate(self._h, C.c_void_p(rec_ptr)))
+
+    def kcenters_step(self, metric, recs_ptr, n_recs, label, cutoff, own_ptr):
+        _lib.check(self.L.ek_feat_kcenters_step(
+            self._h, int(metric), C.c_void_p(recs_ptr), int(n_recs), int(label),
+            float(cutoff), C.c_void_p(own_ptr)))
+
+    def history(self, first, count):
+        """-> (global indices int64 [count], distances float64 [count], n_done)"""
+        idx = np.empty(max(int(count), 1), dtype=np.int64)
+        cd = np.empty(max(int(count), 1), dtype=np.float64)
+        n_done = C.c_int32()
+        _lib.check(self.L.ek_feat_history_download(
+            self._h, int(first), int(count), _lib.i64p(idx), _lib.f64p(cd),
+            C.byref(n_done)))
+        return idx[:count], cd[:count], n_done.value
+
+    def reset_history(self):
+        _lib.check(self.L.ek_feat_history_reset(self._h))
+
+    def close(self):
+        if self._h:
+            self.L.ek_feat_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def _working_dtype(X, hamming):
     if hamming:
         if not np.issubdtype(X.dtype, np.integer):

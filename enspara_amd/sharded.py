@@ -19,6 +19,15 @@ frame numbers instead of the reference's (rank, local index) pairs.
 The driver is written against a small shard protocol so that the same loop
 runs on CPU with the "gloo" backend in tests (tests/test_sharded_gloo.py
 plugs in a checker-backed shard); the product shard is :class:`DeviceShard`.
+
+Feature metrics ('euclidean', 'manhattan', libdist.hamming on a 2-D array of
+samples) shard the same way: :class:`FeatureShard` speaks the one-record part
+of the protocol over an ``ek_feat`` handle -- record = (float64 local max
+distance, global index, that sample's features), one launch per center and
+rank (csrc/ek_features.hip ``feat_shard_step_kernel``) -- and
+:func:`fit_features_sharded` is the estimators' ``mpi_mode`` for them: same
+centers, labels and float64 distances as the single-process loop.  No rounds
+of several candidates, no mailbox transport and no sharded PAM there.
 """
 import numpy as np
 
@@ -238,6 +247,75 @@ class DeviceShard:
 
     def pam_commit(self, accept):
         self.store.pam_commit(accept)
+
+
+class FeatureShard:
+    """The one-record shard protocol (``record_bytes``, ``new_buffer``,
+    ``local_candidate``, ``step``, ``progress``, ``history``,
+    ``reset_history``) on top of a
+    :class:`enspara_amd.geometry.libdist.FeatureStore` for ``metric`` 0
+    euclidean / 1 manhattan / 2 hamming.  As with :class:`DeviceShard` the
+    store lives on a non-default torch stream and the driver runs under
+    ``with torch.cuda.stream(s)``.  No ``candidates``: one center per
+    exchange."""
+
+    def __init__(self, store, metric):
+        import torch
+        self.torch = torch
+        self.store = store
+        self.metric = int(metric)
+        self.device = torch.device("cuda", store.device)
+
+    @property
+    def record_bytes(self):
+        return self.store.record_bytes
+
+    @property
+    def n_local(self):
+        return self.store.n
+
+    @property
+    def offset(self):
+        return self.store.global_offset
+
+    def new_buffer(self, nbytes):
+        return self.torch.empty(nbytes, dtype=self.torch.uint8,
+                                device=self.device)
+
+    def local_candidate(self, rec):
+        self.store.local_candidate(rec.data_ptr())
+
+    def step(self, all_recs, n_recs, label, cutoff, own_rec):
+        self.store.kcenters_step(self.metric, all_recs.data_ptr(), n_recs,
+                                 label, cutoff, own_rec.data_ptr())
+
+    def progress(self):
+        """-> number of centers so far; synchronises"""
+        _, _, n_done = self.store.history(0, 0)
+        return n_done
+
+    def history(self, first, count):
+        return self.store.history(first, count)
+
+    def reset_history(self):
+        self.store.reset_history()
+
+    def distance(self, y):
+        """metric(X_local, y) -> float64 [n_local] on the host (warm start)"""
+        out = np.zeros(self.store.n, dtype=np.float64)
+        self.store.distance(self.metric, y, out)
+        return out
+
+    def reset_state(self):
+        """distances +inf, labels -1"""
+        self.store.reset_state()
+
+    def state(self):
+        """-> (distances float64 [n_local], labels int32 [n_local])"""
+        return self.store.download_state()
+
+    def set_state(self, distances, assignments):
+        self.store.upload_state(distances, assignments)
 
 
 def _to_host(shard, t):
@@ -552,14 +630,21 @@ def warm_start_sharded(shard, init_centers, group=None):
     Every rank passes the same ``init_centers``.  Returns the list of global
     frame indices, one per occupied label in label order: the k-centers loop
     continues from ``first_label = len(result)`` (kcenters.py:306)."""
-    import torch.distributed as dist
-    world, rank = _world(group)
-    collective = dist.is_available() and dist.is_initialized()
     from .cluster.util import _stack_centers
     centers = _stack_centers([c for c in init_centers])
     K0 = int(centers.shape[0])
     shard.assign_nearest(centers)
     d, a = shard.state()
+    return _closest_members(d, a, shard.offset, K0, group)
+
+
+def _closest_members(d, a, offset, K0, group=None):
+    """Per occupied label of 0..K0-1 the member closest to its center, the
+    first such member in the GLOBAL order, from every rank's local (distances,
+    labels): -> global indices in label order (see ``warm_start_sharded``)."""
+    import torch.distributed as dist
+    world, rank = _world(group)
+    collective = dist.is_available() and dist.is_initialized()
     d = np.asarray(d, dtype=np.float64)
     a = np.asarray(a, dtype=np.int64)
     best_d = np.full(K0, np.inf, dtype=np.float64)
@@ -570,7 +655,7 @@ def warm_start_sharded(shard, init_centers, group=None):
         lab = a[order]
         first = np.flatnonzero(np.r_[True, lab[1:] != lab[:-1]])
         best_d[lab[first]] = d[order[first]]
-        best_g[lab[first]] = shard.offset + order[first]
+        best_g[lab[first]] = offset + order[first]
     tables = [(best_d, best_g)]
     if collective and world > 1:
         tables = [None] * world
@@ -1154,3 +1239,160 @@ def fit_sharded(traj, n_clusters=None, dist_cutoff=0.0, n_iters=0,
     return util.ClusterResult(
         center_indices=pairs, assignments=a.astype(np.int64),
         distances=d.astype(np.float64), centers=centers)
+
+
+# ---------------------------------------------------------------------------
+# feature metrics in mpi_mode (euclidean / manhattan / hamming on 2-D samples)
+# ---------------------------------------------------------------------------
+METRIC_NAMES = {0: "euclidean", 1: "manhattan", 2: "hamming"}
+
+
+def _feature_data_problem(X, metric_id):
+    """None if the k-centers loop can run on these samples on the device (what
+    the single-process path's ``resident`` test accepts, cluster/kcenters.py:
+    a 2-D ndarray of floating-point values other than float16 without NaN, or
+    of integers; hamming: integers only), else what is wrong with them."""
+    if not isinstance(X, np.ndarray) or X.ndim != 2:
+        return "the samples must be a 2-D numpy array (got %s)" % (
+            "shape %s" % (X.shape,) if isinstance(X, np.ndarray)
+            else type(X).__name__)
+    if X.shape[1] < 1:
+        return "the samples have no features"
+    integer = np.issubdtype(X.dtype, np.integer)
+    if metric_id == 2:
+        return None if integer else (
+            "hamming distance needs integer samples, got %s" % X.dtype)
+    if integer:
+        return None
+    if not np.issubdtype(X.dtype, np.floating) or X.dtype == np.float16:
+        return "samples of dtype %s" % X.dtype
+    if np.isnan(X).any():
+        return "the samples contain NaN"
+    return None
+
+
+def _device_feature_shard(Xw, metric_id, offset):
+    """The product's shard: a FeatureStore on a torch stream of its own on the
+    current CUDA device, the driver running under that stream."""
+    import contextlib
+    import torch
+    from .geometry.libdist import FeatureStore
+
+    @contextlib.contextmanager
+    def cm():
+        device = torch.cuda.current_device()
+        tstream = torch.cuda.Stream(device=device)
+        with FeatureStore.from_array(Xw, metric_id, device=device,
+                                     global_offset=offset,
+                                     stream=tstream.cuda_stream) as store:
+            with torch.cuda.stream(tstream):
+                yield FeatureShard(store, metric_id)
+    return cm()
+
+
+def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
+                         init_centers=None, group=None, make_shard=None):
+    """k-centers with a feature metric (``metric_id`` 0 euclidean, 1 manhattan,
+    2 hamming) where every rank of the initialised ``torch.distributed`` group
+    passes ITS OWN samples, a 2-D array [n_local, n_features] (n_local may be
+    0) -- ``mpi_mode=True`` of the reference (kcenters.py:314-378) for these
+    metrics: rank r's samples follow rank r-1's in the global order, ties go to
+    the lowest rank, the result is the single-process one.
+
+    Returns a ClusterResult like :func:`fit_sharded`: ``center_indices`` as
+    (rank, local index) pairs, this rank's ``assignments`` (int64) /
+    ``distances`` (float64), ``centers`` = the centers' feature rows in X's
+    dtype, the same list on every rank.  ``init_centers`` (the same rows on
+    every rank) is the warm start of kcenters.py:200-206 by the rule of
+    :func:`warm_start_sharded`; ``centers`` / ``center_indices`` then follow
+    the single-process path (the initial centers, then the new rows; occupied
+    labels' closest members, then the new samples).
+
+    The ranks first compare (n_features, dtype, metric, data usable): on a
+    disagreement EVERY rank raises ImproperlyConfigured, on unusable samples
+    anywhere EVERY rank raises DataInvalid -- a rank raising alone would leave
+    the others waiting in the next collective.  ``make_shard(X, metric_id,
+    offset)`` -> a context manager yielding the shard (tests plug in a
+    numpy-backed one); the default puts the samples on the current CUDA
+    device."""
+    import torch.distributed as dist
+    from .cluster import util
+    from .exception import DataInvalid, ImproperlyConfigured
+    if not (dist.is_available() and dist.is_initialized()):
+        raise ImproperlyConfigured(
+            "mpi_mode needs an initialised torch.distributed process group "
+            "(one process per GPU, e.g. under torchrun)")
+    if metric_id not in METRIC_NAMES:
+        raise ImproperlyConfigured("not a device feature metric: %r"
+                                   % (metric_id,))
+    world, rank = _world(group)
+    problem = _feature_data_problem(X, metric_id)
+    mine = (int(X.shape[0]) if problem is None else 0,
+            int(X.shape[1]) if problem is None else -1,
+            str(X.dtype) if problem is None else "", int(metric_id), problem)
+    everyone = [None] * world
+    dist.all_gather_object(everyone, mine, group=group)
+    bad = [(r, e[4]) for r, e in enumerate(everyone) if e[4] is not None]
+    if bad:
+        raise DataInvalid(
+            "mpi_mode with metric '%s' cannot run on these samples: %s"
+            % (METRIC_NAMES[metric_id],
+               "; ".join("rank %d: %s" % b for b in bad)))
+    if len(set(e[1:4] for e in everyone)) != 1:
+        raise ImproperlyConfigured(
+            "the ranks disagree on (n_features, dtype, metric): %s"
+            % ", ".join("rank %d: (%d, %s, %s)"
+                        % (r, e[1], e[2], METRIC_NAMES.get(e[3], e[3]))
+                        for r, e in enumerate(everyone)))
+    counts = [e[0] for e in everyone]
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    n_total = int(starts[-1])
+    if n_total == 0:
+        raise ValueError("cannot cluster an empty set of samples")
+    lo, hi = int(starts[rank]), int(starts[rank + 1])
+    if make_shard is None:
+        make_shard = _device_feature_shard
+    with make_shard(X, metric_id, lo) as shard:
+        if init_centers is None:
+            centers, med = [], []
+            shard.reset_state()
+        else:
+            centers = [c for c in init_centers]
+            # util.assign_to_nearest_center (util.py:199-203): label 0 / +inf,
+            # then every center in order, strict <
+            d = np.full(hi - lo, np.inf, dtype=np.float64)
+            a = np.zeros(hi - lo, dtype=np.int32)
+            for i, c in enumerate(centers):
+                dc = shard.distance(np.asarray(c))
+                closer = dc < d
+                d[closer] = dc[closer]
+                a[closer] = i
+            shard.set_state(d, a)
+            med = _closest_members(d, a, lo, len(centers), group)
+        budget = (np.inf if n_clusters is None else n_clusters) - len(med)
+        max_new = (0 if budget <= 0 else
+                   (2 * n_total + 16 if np.isinf(budget) else int(budget)))
+        idx, _ = kcenters_sharded(shard, len(med), max_new,
+                                  float(dist_cutoff or 0.0), group=group)
+        med = med + [int(g) for g in idx]
+        d, a = shard.state()
+    # the new centers' rows, from their owners, in X's dtype
+    first_new = len(med) - len(idx)
+    rows = {k: X[med[k] - lo].copy() for k in range(first_new, len(med))
+            if lo <= med[k] < hi}
+    tables = [None] * world
+    dist.all_gather_object(tables, rows, group=group)
+    for t in tables:
+        rows.update(t)
+    new_centers = [rows[k] for k in range(first_new, len(med))]
+    if init_centers is None:
+        centers = new_centers
+    else:
+        centers = centers + new_centers
+    pairs = []
+    for g in med:
+        r = int(np.searchsorted(starts, g, side="right") - 1)
+        pairs.append((r, int(g - starts[r])))
+    return util.ClusterResult(
+        center_indices=pairs, assignments=np.asarray(a).astype(np.int64),
+        distances=np.asarray(d, dtype=np.float64), centers=centers)

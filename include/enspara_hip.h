@@ -577,6 +577,51 @@ int ek_feat_kcenters(ek_feat *k, int32_t metric, int32_t first_label,
                      int32_t max_new, double dist_cutoff, double *dist_io,
                      int32_t *assign_io, int64_t *centers_out, int32_t *n_added,
                      double *final_max);
+/* ---- the same loop over several shards (one ek_feat handle each) ----------------
+ * The reference's MPI iteration (kcenters.py:314-378) for a feature metric:
+ * every shard owns a contiguous block of the samples, `global_offset` is the
+ * global index of its first one.  Per center every shard contributes ONE
+ * candidate record, ek_feat_record_bytes(n_features, elem_kind) long (a multiple
+ * of 16):
+ *   { double max_dist; int64_t global_index; T row[n_features] }
+ * max_dist = the maximum of the shard's float64 distances, global_index =
+ * global_offset + the first local index of that maximum, row = that sample's
+ * features in the samples' own element kind; a shard without samples writes
+ * max_dist = -inf.  The caller exchanges the records (one all-gather);
+ * ek_feat_kcenters_step is ONE launch: every workgroup picks the winner among
+ * the n_recs records at all_recs_dev (largest max_dist, lowest record index
+ * among equal ones -- with the shards in rank order np.argmax's first index over
+ * the concatenated data), applies the stop rule `!(max > dist_cutoff)` to it (so
+ * that every shard stops at the same label; later steps return at once),
+ * computes metric(X_local, row) with the arithmetic of ek_feat_distance, applies
+ * the strict-< update with `label`, and the workgroup that arrives last writes
+ * the shard's next record to own_rec_dev (which may be the shard's slot of
+ * all_recs_dev only where n_recs == 1) and appends (winner's global index, its
+ * max_dist) to the history.  All pointers named *_dev are device memory; the
+ * launches go to the handle's stream: `stream` of ek_feat_create_sharded (a
+ * hipStream_t the caller keeps alive; NULL: a stream of the handle's own), so
+ * that a caller's collectives on that stream are ordered with them.
+ * ek_feat_state_reset: distances +inf, labels -1, history empty;
+ * ek_feat_state_upload / _download: float64 [n_samples], int32 [n_samples];
+ * ek_feat_local_candidate: the record of the state as it stands (once before the
+ * loop, after a reset or an upload); ek_feat_history_download: entries
+ * [first, first + count) (index -1 where none) and *n_done = last label + 1. */
+size_t ek_feat_record_bytes(int32_t n_features, int32_t elem_kind);
+int ek_feat_create_sharded(int device, int64_t n_samples, int32_t n_features,
+                           int32_t elem_kind, int64_t global_offset, void *stream,
+                           ek_feat **out);
+int ek_feat_state_reset(ek_feat *k);
+int ek_feat_state_upload(ek_feat *k, const double *dist_host,
+                         const int32_t *assign_host);
+int ek_feat_state_download(ek_feat *k, double *dist_host, int32_t *assign_host);
+int ek_feat_local_candidate(ek_feat *k, void *rec_dev);
+int ek_feat_kcenters_step(ek_feat *k, int32_t metric, const void *all_recs_dev,
+                          int32_t n_recs, int32_t label, double dist_cutoff,
+                          void *own_rec_dev);
+int ek_feat_history_download(ek_feat *k, int32_t first, int32_t count,
+                             int64_t *center_index_out, double *center_dist_out,
+                             int32_t *n_done);
+int ek_feat_history_reset(ek_feat *k);
 /* One PAM sweep (reference kmedoids.py:575-699, serial branch) over clusters
  * *cid .. n_medoids - 1 for metric 0 (euclidean) / 1 (manhattan), with the
  * float64 distances, the labels and the medoids' features resident on the device:

@@ -418,7 +418,7 @@ msm_cells_kernel(const int32_t *__restrict__ table, int64_t n_cells,
 // scratch of a count, kept between calls by a context (hipMalloc costs more than
 // the kernels)
 struct EkMsmScratch {
-    int32_t *c = nullptr;       // squeezed labels [n + lag]
+    int32_t *c = nullptr;       // squeezed labels [n]
     int32_t *cnt = nullptr;     // per-workgroup counts
     int64_t *off = nullptr;     // their prefix sums
     int64_t *start = nullptr, *cstart = nullptr;    // [n_trj + 1]
@@ -489,7 +489,9 @@ static int msm_counts_device(hipStream_t s, EkMsmScratch &w, const int32_t *d_a,
         int64_t cap_rows = w.cap_out, cap_cols = w.cap_out, cap_vals = w.cap_out;
         int64_t cap_cnt = w.cap_blocks, cap_off = w.cap_blocks ? w.cap_blocks + 1 : 0;
         int64_t cap_start = w.cap_trj, cap_cstart = w.cap_trj, cap_bad = w.bad ? 1 : 0;
-        hipError_t e = msm_grow(w.c, w.cap_c, n + lag_time);
+        // (every read of c[p + lag] is guarded by p + lag < m <= n: n labels, whatever
+        // the lag)
+        hipError_t e = msm_grow(w.c, w.cap_c, n);
         if (e == hipSuccess)
             e = msm_grow(w.cnt, cap_cnt, std::max(nb, ncb));
         if (e == hipSuccess)

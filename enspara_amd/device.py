@@ -452,6 +452,9 @@ class FrameStore:
         do not leave the device (reference flow: cluster -> assigns_to_counts,
         enspara/msm/transition_matrices.py:113-170)."""
         lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+        for name, v in (("lag_time", lag_time), ("n_states", n_states)):
+            if not 1 <= int(v) < 2 ** 31:       # (ctypes would wrap it silently)
+                raise DataInvalid("%s=%d is outside [1, 2^31)" % (name, int(v)))
         cap = max(1, min(int(self.n), int(n_states) * int(n_states)))
         rows = np.empty(cap, dtype=np.int32)
         cols = np.empty(cap, dtype=np.int32)

@@ -40,6 +40,32 @@ def _rows_of(assigns):
     return flat, lengths
 
 
+_INT32_MAX = 2 ** 31 - 1
+
+
+def _int32_arg(name, value):
+    """`value` as an int the C ABI's int32 holds (ctypes would wrap it silently)"""
+    value = int(value)
+    if not -_INT32_MAX - 1 <= value <= _INT32_MAX:
+        raise DataInvalid("%s=%d does not fit in 32 bits" % (name, value))
+    return value
+
+
+def _n_states_arg(max_n_states):
+    max_n_states = int(max_n_states)
+    if not 0 <= max_n_states <= _INT32_MAX:
+        raise DataInvalid("max_n_states=%d is outside [0, 2^31): the state labels "
+                          "are int32" % max_n_states)
+    return max_n_states
+
+
+def _lag_spans_nothing(lag_time, lengths):
+    """no trajectory is longer than the lag: a[:-lag] is empty for every one of them
+    (reference :310-321), whatever the labels are -- and every lag the library is
+    asked for is below a frame count, so it fits its int32"""
+    return lag_time >= max((int(v) for v in lengths), default=0)
+
+
 def assigns_to_counts(assigns, lag_time, max_n_states=None,
                       sliding_window=True, device=0, lengths=None):
     """Count transitions (reference transition_matrices.py:113-170).
@@ -69,8 +95,9 @@ def assigns_to_counts(assigns, lag_time, max_n_states=None,
         if sum(int(v) for v in lengths) != assigns.n:
             raise DataInvalid("lengths add up to %d frames, the store holds %d"
                               % (sum(int(v) for v in lengths), assigns.n))
-        max_n_states = int(max_n_states)
-        if max_n_states == 0 or assigns.n == 0:
+        max_n_states = _n_states_arg(max_n_states)
+        if max_n_states == 0 or assigns.n == 0 or \
+                _lag_spans_nothing(lag_time, lengths):
             return scipy.sparse.coo_matrix((max_n_states, max_n_states),
                                            dtype=int)
         r, c, v = assigns.msm_counts(lengths, lag_time, max_n_states,
@@ -81,15 +108,18 @@ def assigns_to_counts(assigns, lag_time, max_n_states=None,
     if max_n_states is None:
         kept = flat[flat != -1]
         max_n_states = int(kept.max()) + 1 if kept.size else 0
-    max_n_states = int(max_n_states)
+    max_n_states = _n_states_arg(max_n_states)
     if flat.size:
         lo, hi = int(flat.min()), int(flat.max())
         if lo < -1:
             raise ValueError("negative row index found")   # scipy's wording
         if hi >= max_n_states:
             raise ValueError("row index exceeds matrix dimensions")
-    if max_n_states == 0 or flat.size == 0:
+    if max_n_states == 0 or flat.size == 0 or _lag_spans_nothing(lag_time, lengths):
         return scipy.sparse.coo_matrix((max_n_states, max_n_states), dtype=int)
+    if flat.size > _INT32_MAX:
+        raise DataInvalid("%d frames: a cell of the int32 count table could "
+                          "overflow" % flat.size)
     a32 = np.ascontiguousarray(flat, dtype=np.int32)
     cap = max(1, int(a32.size))
     rows = np.empty(cap, dtype=np.int32)
@@ -98,8 +128,9 @@ def assigns_to_counts(assigns, lag_time, max_n_states=None,
     nnz = C.c_int64()
     L = _lib.load()
     _lib.check(L.ek_msm_counts(
-        int(device), _lib.i32p(a32), _lib.i64p(lengths), len(lengths),
-        int(lag_time), 1 if sliding_window else 0, max_n_states, cap,
+        _int32_arg("device", device), _lib.i32p(a32), _lib.i64p(lengths),
+        len(lengths), _int32_arg("lag_time", lag_time),
+        1 if sliding_window else 0, max_n_states, cap,
         _lib.i32p(rows), _lib.i32p(cols), _lib.i64p(vals), C.byref(nnz)))
     k = nnz.value
     return scipy.sparse.coo_matrix(

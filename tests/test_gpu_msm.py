@@ -343,6 +343,7 @@ def test_counts_gathered_in_lds_equal_one_atomic_per_transition(tmp_path):
     short, empty and all-(-1) trajectories, with and without the sliding window"""
     import subprocess
     import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     got = {}
     for form in ("1", "0"):
@@ -363,3 +364,25 @@ def test_counts_gathered_in_lds_equal_one_atomic_per_transition(tmp_path):
     A = (rng.randint(K, size=(40, 1)) + np.cumsum(steps, axis=1)) % K
     A[rng.rand(*A.shape) < 0.002] = -1
     np.testing.assert_array_equal(got["1"]["c0"], np.asarray(_scipy_counts(A, 1, K).todense()))
+    # and all five against the plain numpy reference (tests/_numpy_msm.py): the two
+    # forms share the trajectory lookup, so their agreeing says nothing about it
+    import _numpy_msm as nm
+    B = rng.randint(300, size=(6, 100000))
+    lens = rng.randint(0, 90, size=4000)
+    lens[::17] = 0
+    flat = rng.randint(50, size=int(lens.sum()))
+    flat[rng.rand(len(flat)) < 0.05] = -1
+
+    def dense(coo, K):
+        out = np.zeros((K, K), dtype=np.int64)
+        out[coo[0], coo[1]] = coo[2]
+        return out
+    whole = lambda X: (X.reshape(-1), np.full(X.shape[0], X.shape[1]))  # noqa: E731
+    want = [dense(nm.counts_ref(*whole(A), 1, True, K), K),
+            dense(nm.counts_ref(*whole(A), 7, False, K), K),
+            dense(nm.counts_ref(*whole(B), 3, True, 300), 300),
+            dense(nm.counts_ref(flat, lens, 2, True, 50), 50),
+            dense(nm.counts_ref(flat, lens, 40, True, 50), 50)]
+    for i, w in enumerate(want):
+        for form in ("1", "0"):
+            np.testing.assert_array_equal(got[form]["c%d" % i], w)

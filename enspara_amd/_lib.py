@@ -53,6 +53,8 @@ SYMBOLS = [
     "ek_feat_record_bytes", "ek_feat_create_sharded", "ek_feat_state_reset",
     "ek_feat_state_upload", "ek_feat_state_download", "ek_feat_local_candidate",
     "ek_feat_kcenters_step", "ek_feat_history_download", "ek_feat_history_reset",
+    "ek_feat_pam_count_batch", "ek_feat_pam_select_batch", "ek_feat_pam_gather_rows",
+    "ek_feat_pam_begin", "ek_feat_pam_propose", "ek_feat_pam_commit",
     "ek_set_frames_per_lane", "ek_set_option", "ek_get_option", "ek_last_run_timing",
     "ek_reserve_centers",
     "ek_debug_guards",
@@ -237,6 +239,12 @@ def load():
     L.ek_feat_kcenters_step.argtypes = [vp, i32, vp, i32, i32, C.c_double, vp]
     L.ek_feat_history_download.argtypes = [vp, i32, i32, i64p, f64p, i32p]
     L.ek_feat_history_reset.argtypes = [vp]
+    L.ek_feat_pam_count_batch.argtypes = [vp, i32, i32, i64p]
+    L.ek_feat_pam_select_batch.argtypes = [vp, i32, i32, i64p, i64p]
+    L.ek_feat_pam_gather_rows.argtypes = [vp, i32, i64p, i64p, vp]
+    L.ek_feat_pam_begin.argtypes = [vp, i32, vp, i32]
+    L.ek_feat_pam_propose.argtypes = [vp, i32, vp, i32, i32, vp]
+    L.ek_feat_pam_commit.argtypes = [vp, i32]
     L.ek_set_frames_per_lane.argtypes = [vp, C.c_int]
     L.ek_set_option.argtypes = [vp, i32, i32]
     L.ek_get_option.argtypes = [vp, i32, i32p]

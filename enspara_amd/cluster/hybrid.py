@@ -59,10 +59,26 @@ def hybrid(X, distance_method, n_iters=5, n_clusters=np.inf, dist_cutoff=0,
     distance_method = util._get_distance_method(distance_method)
     if not util.is_device_rmsd(distance_method):
         if mpi_mode:
-            raise ImproperlyConfigured(
-                "KHybrid in MPI mode runs metric 'rmsd' on the device; there is "
-                "no sharded PAM sweep for a feature or callable metric "
-                "(KCenters has an mpi_mode for 'euclidean' / 'manhattan')")
+            # hybrid.py:112-162 in MPI mode for the device feature metrics:
+            # every rank passes its own samples
+            mid = getattr(distance_method, "device_metric_id", None)
+            if mid is None:
+                raise ImproperlyConfigured(
+                    "KHybrid in MPI mode runs metric 'rmsd' and the device "
+                    "feature metrics ('euclidean', 'manhattan', "
+                    "libdist.hamming); there is no sharded PAM sweep for a "
+                    "callable metric")
+            if (n_clusters is None or n_clusters is np.inf) and not dist_cutoff:
+                raise ImproperlyConfigured("Either n_clusters or cluster_radius "
+                                           "is required for KHybrid clustering")
+            if random_first_center:
+                raise NotImplementedError(
+                    "We haven't implemented kcenters 'random_first_center' yet.")
+            from .. import sharded
+            return sharded.fit_features_sharded(
+                X, mid, n_clusters=n_clusters, dist_cutoff=dist_cutoff or 0.0,
+                init_centers=init_centers, n_iters=n_iters,
+                random_state=random_state)
         result = _kc.kcenters(
             X, distance_method, n_clusters=n_clusters, dist_cutoff=dist_cutoff,
             init_centers=init_centers,

@@ -97,10 +97,12 @@ def kmedoids(X, distance_method, n_clusters=None, n_iters=5, assignments=None,
                 " (assignments and distances) for KMedoids")
     distance_method = util._get_distance_method(distance_method)
     if mpi_mode:
-        if not util.is_device_rmsd(distance_method):
+        mid = getattr(distance_method, "device_metric_id", None)
+        if not util.is_device_rmsd(distance_method) and mid is None:
             raise ImproperlyConfigured(
-                "KMedoids in MPI mode runs metric 'rmsd' on the device; a "
-                "callable metric has no sharded form here")
+                "KMedoids in MPI mode runs metric 'rmsd' and the device "
+                "feature metrics on the device; a callable metric has no "
+                "sharded form here")
         if args is not None or lengths is not None:
             raise ImproperlyConfigured(
                 "KMedoids in MPI mode takes every rank's own frames; `args` / "
@@ -112,6 +114,12 @@ def kmedoids(X, distance_method, n_clusters=None, n_iters=5, assignments=None,
                 "(%d); device=%r conflicts with it"
                 % (torch.cuda.current_device(), device))
         from .. import sharded
+        if mid is not None and not util.is_device_rmsd(distance_method):
+            return sharded.kmedoids_features_sharded(
+                X, mid, n_clusters=n_clusters, n_iters=n_iters,
+                assignments=assignments, distances=distances,
+                cluster_center_inds=cluster_center_inds, X_lengths=X_lengths,
+                proposals=proposals, random_state=random_state)
         return sharded.kmedoids_fit_sharded(
             X, n_clusters=n_clusters, n_iters=n_iters, assignments=assignments,
             distances=distances, cluster_center_inds=cluster_center_inds,

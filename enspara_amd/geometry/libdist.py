@@ -188,6 +188,46 @@ class FeatureStore(_Resident):
     def reset_history(self):
         _lib.check(self.L.ek_feat_history_reset(self._h))
 
+    # the PAM sweep over several shards (include/enspara_hip.h, "the same sweep
+    # over several shards"): counts / members / rows of THIS shard's samples
+    def pam_count_members_batch(self, cid0, count):
+        """-> int64 [count]: local members of clusters cid0 ..; synchronises"""
+        out = np.zeros(int(count), dtype=np.int64)
+        _lib.check(self.L.ek_feat_pam_count_batch(self._h, int(cid0), int(count),
+                                                  _lib.i64p(out)))
+        return out
+
+    def pam_select_members_batch(self, cid0, js):
+        """-> int64 [len(js)]: the js[j]-th local member of cluster cid0 + j
+        (-1 where js[j] < 0), after the count of the same clusters"""
+        js = np.ascontiguousarray(js, dtype=np.int64)
+        out = np.full(len(js), -1, dtype=np.int64)
+        _lib.check(self.L.ek_feat_pam_select_batch(
+            self._h, int(cid0), len(js), _lib.i64p(js), _lib.i64p(out)))
+        return out
+
+    def pam_gather_rows(self, samples, rows, table_ptr):
+        """table[rows[i]] = features of local sample samples[i] (device table
+        [*, F] in this store's dtype)"""
+        s = np.ascontiguousarray(samples, dtype=np.int64)
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        if len(s) != len(r):
+            raise DataInvalid("%d samples for %d table rows" % (len(s), len(r)))
+        _lib.check(self.L.ek_feat_pam_gather_rows(
+            self._h, len(s), _lib.i64p(s), _lib.i64p(r), C.c_void_p(table_ptr)))
+
+    def pam_begin(self, metric, table_ptr, n_medoids):
+        _lib.check(self.L.ek_feat_pam_begin(self._h, int(metric),
+                                            C.c_void_p(table_ptr), int(n_medoids)))
+
+    def pam_propose(self, cid, row_ptr, win_lo, win_count, out_ptr):
+        _lib.check(self.L.ek_feat_pam_propose(
+            self._h, int(cid), C.c_void_p(row_ptr), int(win_lo), int(win_count),
+            C.c_void_p(out_ptr)))
+
+    def pam_commit(self, accept):
+        _lib.check(self.L.ek_feat_pam_commit(self._h, 1 if accept else 0))
+
     def close(self):
         if self._h:
             self.L.ek_feat_destroy(self._h)

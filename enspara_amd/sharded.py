@@ -317,6 +317,50 @@ class FeatureShard:
     def set_state(self, distances, assignments):
         self.store.upload_state(distances, assignments)
 
+    # PAM across shards, the methods pam_sweep_sharded drives (DeviceShard's):
+    # rows travel as [rows, n_features] tables in the samples' element kind,
+    # the int64 `meta` vector only carries the proposals' global indices
+    host_to_buffer = DeviceShard.host_to_buffer
+    to_host = DeviceShard.to_host
+
+    def new_table(self, rows):
+        t = self.torch
+        dt = {"float32": t.float32, "float64": t.float64,
+              "int64": t.int64}[np.dtype(self.store.dtype).name]
+        return (t.zeros((rows, self.store.F), dtype=dt, device=self.device),
+                t.zeros(2 * rows, dtype=t.int64, device=self.device))
+
+    def fill_rows(self, local_samples, rows, table, meta):
+        if len(local_samples):
+            self.store.pam_gather_rows(local_samples, rows, table.data_ptr())
+
+    def pam_begin_table(self, table, meta, n_medoids):
+        self.store.pam_begin(self.metric, table.data_ptr(), n_medoids)
+
+    def pam_count_batch(self, cid0, count):
+        return self.store.pam_count_members_batch(cid0, count)
+
+    def pam_select_batch(self, cid0, js):
+        return self.store.pam_select_members_batch(cid0, js)
+
+    def pam_count(self, cid):
+        return self.store.pam_count_members_batch(cid, 1)[0]
+
+    def pam_select(self, cid, j):
+        return self.store.pam_select_members_batch(cid, [j])[0]
+
+    def pam_prefetch_centers(self, table, meta, count, win_lo=0, win_count=0):
+        """(nothing to prepare: a proposal reads its row from the table)"""
+
+    def pam_propose_center(self, cid, slot, table, meta, row, n_members_local,
+                           win_lo, win_count, out):
+        self.store.pam_propose(
+            cid, table.data_ptr() + row * table.stride(0) * table.element_size(),
+            win_lo, win_count, out.data_ptr())
+
+    def pam_commit(self, accept):
+        self.store.pam_commit(accept)
+
 
 def _to_host(shard, t):
     f = getattr(shard, "to_host", None)
@@ -1290,38 +1334,57 @@ def _device_feature_shard(Xw, metric_id, offset):
     return cm()
 
 
-def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
-                         init_centers=None, group=None, make_shard=None):
-    """k-centers with a feature metric (``metric_id`` 0 euclidean, 1 manhattan,
-    2 hamming) where every rank of the initialised ``torch.distributed`` group
-    passes ITS OWN samples, a 2-D array [n_local, n_features] (n_local may be
-    0) -- ``mpi_mode=True`` of the reference (kcenters.py:314-378) for these
-    metrics: rank r's samples follow rank r-1's in the global order, ties go to
-    the lowest rank, the result is the single-process one.
+_PAM_WHAT = "the sharded PAM sweep"
 
-    Returns a ClusterResult like :func:`fit_sharded`: ``center_indices`` as
-    (rank, local index) pairs, this rank's ``assignments`` (int64) /
-    ``distances`` (float64), ``centers`` = the centers' feature rows in X's
-    dtype, the same list on every rank.  ``init_centers`` (the same rows on
-    every rank) is the warm start of kcenters.py:200-206 by the rule of
-    :func:`warm_start_sharded`; ``centers`` / ``center_indices`` then follow
-    the single-process path (the initial centers, then the new rows; occupied
-    labels' closest members, then the new samples).
 
-    The ranks first compare (n_features, dtype, metric, data usable): on a
-    disagreement EVERY rank raises ImproperlyConfigured, on unusable samples
-    anywhere EVERY rank raises DataInvalid -- a rank raising alone would leave
-    the others waiting in the next collective.  ``make_shard(X, metric_id,
-    offset)`` -> a context manager yielding the shard (tests plug in a
-    numpy-backed one); the default puts the samples on the current CUDA
-    device."""
+def _agree_on_seed(random_state, group, world):
+    """The sweeps draw member ranks from ONE stream that every rank replays
+    (the reference agrees on each draw, mpi/ops.py randind): ranks that pass
+    different seeds or differently positioned RandomStates would propose
+    different samples and wait for each other forever, so they compare first
+    and raise ImproperlyConfigured together.  None everywhere (also the global
+    numpy RandomState, what the estimators make of None): rank 0's draw for
+    all.  -> RandomState"""
+    import hashlib
     import torch.distributed as dist
-    from .cluster import util
+    from .cluster.kcenters import check_random_state
+    from .exception import ImproperlyConfigured
+    if random_state is None or random_state is np.random.mtrand._rand:
+        mark = None
+    elif isinstance(random_state, (int, np.integer)):
+        mark = ("seed", int(random_state))
+    elif isinstance(random_state, np.random.RandomState):
+        st = random_state.get_state()
+        mark = ("state", hashlib.sha1(np.asarray(st[1]).tobytes()).hexdigest(),
+                int(st[2]))
+    else:
+        mark = ("other", repr(random_state))
+    draw = int(np.random.SeedSequence().entropy % (2 ** 31 - 1))
+    everyone = [None] * world
+    dist.all_gather_object(everyone, (mark, draw), group=group)
+    if len(set(m for m, _ in everyone)) != 1:
+        raise ImproperlyConfigured(
+            "the ranks disagree on random_state (%s): the sharded PAM sweep "
+            "needs the same seed, or identically seeded RandomStates, on "
+            "every rank" % ", ".join(
+                "rank %d: %s" % (r, "None" if m is None else m[0] + " " +
+                                 str(m[1])[:12]) for r, (m, _) in
+                enumerate(everyone)))
+    if mark is None:
+        return check_random_state(everyone[0][1])
+    return check_random_state(random_state)
+
+
+def _agree_on_samples(X, metric_id, group, what="mpi_mode"):
+    """The pre-loop agreement of the feature drivers: the ranks compare
+    (n_features, dtype, metric, data usable) and raise TOGETHER, see
+    :func:`fit_features_sharded`.  -> (world, rank, starts int64 [world + 1])"""
+    import torch.distributed as dist
     from .exception import DataInvalid, ImproperlyConfigured
     if not (dist.is_available() and dist.is_initialized()):
         raise ImproperlyConfigured(
-            "mpi_mode needs an initialised torch.distributed process group "
-            "(one process per GPU, e.g. under torchrun)")
+            "%s needs an initialised torch.distributed process group "
+            "(one process per GPU, e.g. under torchrun)" % what)
     if metric_id not in METRIC_NAMES:
         raise ImproperlyConfigured("not a device feature metric: %r"
                                    % (metric_id,))
@@ -1349,6 +1412,49 @@ def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
     n_total = int(starts[-1])
     if n_total == 0:
         raise ValueError("cannot cluster an empty set of samples")
+    return world, rank, starts
+
+
+def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
+                         init_centers=None, group=None, make_shard=None,
+                         n_iters=0, random_state=None):
+    """k-centers with a feature metric (``metric_id`` 0 euclidean, 1 manhattan,
+    2 hamming) where every rank of the initialised ``torch.distributed`` group
+    passes ITS OWN samples, a 2-D array [n_local, n_features] (n_local may be
+    0) -- ``mpi_mode=True`` of the reference (kcenters.py:314-378) for these
+    metrics: rank r's samples follow rank r-1's in the global order, ties go to
+    the lowest rank, the result is the single-process one.
+
+    Returns a ClusterResult like :func:`fit_sharded`: ``center_indices`` as
+    (rank, local index) pairs, this rank's ``assignments`` (int64) /
+    ``distances`` (float64), ``centers`` = the centers' feature rows in X's
+    dtype, the same list on every rank.  ``init_centers`` (the same rows on
+    every rank) is the warm start of kcenters.py:200-206 by the rule of
+    :func:`warm_start_sharded`; ``centers`` / ``center_indices`` then follow
+    the single-process path (the initial centers, then the new rows; occupied
+    labels' closest members, then the new samples).
+
+    ``n_iters`` > 0: that many PAM sweeps follow (k-hybrid, hybrid.py:112-162
+    in MPI mode; :func:`pam_sweep_sharded` over the shard's ``pam_*`` methods),
+    one random stream across them from ``random_state`` -- the same int seed or
+    identically seeded RandomState on every rank (:func:`_agree_on_seed`);
+    ``centers`` are then the medoids' rows.  A cluster without members makes
+    ``RandomState.choice`` raise on every rank in the same proposal.
+
+    The ranks first compare (n_features, dtype, metric, data usable): on a
+    disagreement EVERY rank raises ImproperlyConfigured, on unusable samples
+    anywhere EVERY rank raises DataInvalid -- a rank raising alone would leave
+    the others waiting in the next collective.  ``make_shard(X, metric_id,
+    offset)`` -> a context manager yielding the shard (tests plug in a
+    numpy-backed one); the default puts the samples on the current CUDA
+    device."""
+    import torch.distributed as dist
+    from .cluster import util
+    world, rank, starts = _agree_on_samples(
+        X, metric_id, group, _PAM_WHAT if n_iters else "mpi_mode")
+    n_total = int(starts[-1])
+    rs = (_agree_on_seed(random_state, group, world) if int(n_iters) > 0
+          else None)
     lo, hi = int(starts[rank]), int(starts[rank + 1])
     if make_shard is None:
         make_shard = _device_feature_shard
@@ -1375,9 +1481,12 @@ def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
         idx, _ = kcenters_sharded(shard, len(med), max_new,
                                   float(dist_cutoff or 0.0), group=group)
         med = med + [int(g) for g in idx]
+        for _ in range(int(n_iters)):
+            med = pam_sweep_sharded(shard, med, random_state=rs, group=group)
         d, a = shard.state()
-    # the new centers' rows, from their owners, in X's dtype
-    first_new = len(med) - len(idx)
+    # the new centers' rows (after PAM sweeps: every medoid's), from their
+    # owners, in X's dtype
+    first_new = 0 if int(n_iters) > 0 else len(med) - len(idx)
     rows = {k: X[med[k] - lo].copy() for k in range(first_new, len(med))
             if lo <= med[k] < hi}
     tables = [None] * world
@@ -1385,7 +1494,7 @@ def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
     for t in tables:
         rows.update(t)
     new_centers = [rows[k] for k in range(first_new, len(med))]
-    if init_centers is None:
+    if init_centers is None or int(n_iters) > 0:
         centers = new_centers
     else:
         centers = centers + new_centers
@@ -1396,3 +1505,169 @@ def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
     return util.ClusterResult(
         center_indices=pairs, assignments=np.asarray(a).astype(np.int64),
         distances=np.asarray(d, dtype=np.float64), centers=centers)
+
+
+def kmedoids_features_sharded(X, metric_id, n_clusters=None, n_iters=5,
+                              assignments=None, distances=None,
+                              cluster_center_inds=None, X_lengths=None,
+                              proposals=None, random_state=None, group=None,
+                              make_shard=None):
+    """``kmedoids()`` / ``KMedoids.fit`` in mpi_mode for a feature metric
+    (``metric_id`` 0 euclidean, 1 manhattan, 2 hamming): every rank passes ITS
+    OWN samples [n_local, n_features], the counterpart of
+    :func:`kmedoids_sharded` for RMSD with the same two starts.
+
+    Warm start: this rank's ``assignments`` / ``distances`` and the same
+    ``cluster_center_inds`` on every rank.  With ``X_lengths`` (the lengths of
+    ALL trajectories, striped over the ranks t % world) they are flat indices
+    into the concatenation of all trajectories or (trajectory, frame) pairs
+    (:func:`ctr_ids_mpi`); without it, flat indices in the ranks' order (rank
+    r's samples after rank r-1's).  Cold start: ``n_clusters`` distinct samples
+    from ``np.random.default_rng(seed)`` over all samples like the
+    single-process path, then every sample to its nearest (strict <, lowest
+    label on ties).  Supplying only some of the three raises the reference's
+    ImproperlyConfigured.
+
+    ``proposals``: (rank, local index) pairs, one per cluster.  Returns a
+    ClusterResult shaped like :func:`fit_features_sharded`'s.  Collective:
+    every rank calls it, and every check that can fail on one rank alone is
+    exchanged first so that all ranks raise together."""
+    import torch.distributed as dist
+    from .cluster import util
+    from .cluster.kcenters import check_random_state
+    from .exception import DataInvalid, ImproperlyConfigured
+    world, rank, starts = _agree_on_samples(X, metric_id, group, _PAM_WHAT)
+    n_total = int(starts[-1])
+    lo, hi = int(starts[rank]), int(starts[rank + 1])
+    # every check of this rank's own arguments is exchanged before anyone
+    # raises: a rank raising alone would leave the others in a collective
+    given = [assignments is not None, distances is not None,
+             cluster_center_inds is not None]
+    warm = all(given)
+    err = None                  # (exception class, message)
+    med, d0, a0 = None, None, None
+    if any(given) and not warm:
+        err = (ImproperlyConfigured,
+               "For KMedoids, MPI mode can start from scratch without "
+               "assignments, distances, or cluster_center_inds. "
+               "Or, it requires that all are supplied.")
+    elif not warm and n_clusters is None:
+        err = (ImproperlyConfigured,
+               "Must provide n_clusters or cluster_center_inds, assignments,"
+               "and distances for KMedoids in MPI mode.")
+    elif warm:
+        try:
+            if X_lengths is not None:
+                mine_len = sum(int(v) for v in X_lengths[rank::world])
+                if mine_len != hi - lo:
+                    raise DataInvalid(
+                        "rank %d holds %d samples, but the trajectories "
+                        "X_lengths gives it (t %% %d == %d) have %d"
+                        % (rank, hi - lo, world, rank, mine_len))
+                pairs0 = ctr_ids_mpi(cluster_center_inds, X_lengths, world)
+                med = [int(starts[r]) + i for r, i in pairs0]
+            elif hasattr(cluster_center_inds[0], "__len__"):
+                raise ImproperlyConfigured(
+                    "If cluster_center_inds is given as [[global_traj_id, "
+                    "frame_id],...] then X_lengths also needs to be supplied")
+            else:
+                med = [int(g) for g in cluster_center_inds]
+                if min(med) < 0 or max(med) >= n_total:
+                    raise IndexError("cluster center index outside the %d "
+                                     "samples of all ranks" % n_total)
+            d0 = np.asarray(distances, dtype=np.float64)
+            a0 = np.asarray(assignments)
+            if len(d0) != hi - lo or len(a0) != hi - lo:
+                raise DataInvalid(
+                    "rank %d: %d assignments / %d distances for %d samples"
+                    % (rank, len(a0), len(d0), hi - lo))
+            mine = [g - lo for g in med if lo <= g < hi]
+            # the medoids must sit at (numerically) zero distance
+            # (kmedoids.py:185-187)
+            if not np.all(d0[mine] < 0.001):
+                raise DataInvalid(
+                    "rank %d: cluster_center_inds name samples that are not "
+                    "at distance 0 from their cluster's center (max %g)"
+                    % (rank, float(np.max(d0[mine]))))
+        except (DataInvalid, ImproperlyConfigured, IndexError) as e:
+            err = (type(e), str(e))
+    K = (len(med) if med is not None else
+         (int(n_clusters) if n_clusters is not None else 0))
+    if err is None and proposals is not None:
+        if len(proposals) != K:
+            err = (DataInvalid,
+                   "Length of 'proposals' didn't match length of 'medoid_inds' "
+                   "({} != {}).".format(len(proposals), K))
+        elif not hasattr(proposals[0], "__len__"):
+            err = (DataInvalid,
+                   "Depth of 'proposals' didn't match 'medoid_inds' "
+                   "(proposals[0] == {}, whereas medoid_inds[0] == {})".format(
+                       proposals[0], (0, 0)))
+    said = [None] * world
+    dist.all_gather_object(
+        said, (err, warm, K, proposals is not None, int(n_iters)), group=group)
+    bad = [(r, e[0]) for r, e in enumerate(said) if e[0] is not None]
+    if bad:
+        raise bad[0][1][0]("; ".join(
+            m if m.startswith("rank ") else "rank %d: %s" % (r, m)
+            for r, (_, m) in bad))
+    if len(set(e[1:] for e in said)) != 1:
+        raise ImproperlyConfigured(
+            "the ranks disagree on the start (warm, clusters, proposals given, "
+            "n_iters): %s" % ", ".join("rank %d: %s" % (r, e[1:])
+                                       for r, e in enumerate(said)))
+    # one random_state for all: the cold start's draw of the medoids and the
+    # sweeps' draws of members both have to be the same on every rank
+    rs = _agree_on_seed(random_state, group, world)
+    if not warm:
+        seed = random_state
+        if seed is None or not isinstance(seed, (int, np.integer)):
+            draw = (np.random.SeedSequence().entropy % (2 ** 62) if seed is None
+                    else int(check_random_state(seed).randint(0, 2 ** 31 - 1)))
+            seeds = [None] * world
+            dist.all_gather_object(seeds, int(draw), group=group)
+            seed = seeds[0]
+        rng = np.random.default_rng(seed=int(seed))
+        med = np.array([])
+        while len(np.unique(med)) < int(n_clusters):
+            med = rng.integers(0, n_total, int(n_clusters))
+        med = [int(g) for g in med]
+    prop = None
+    if proposals is not None:
+        prop = [int(starts[int(r)]) + int(i) for r, i in proposals]
+
+    def rows_of(which):
+        rows = {k: X[g - lo].copy() for k, g in enumerate(which)
+                if lo <= g < hi}
+        tables = [None] * world
+        dist.all_gather_object(tables, rows, group=group)
+        for t in tables:
+            rows.update(t)
+        return [rows[k] for k in range(len(which))]
+
+    if make_shard is None:
+        make_shard = _device_feature_shard
+    with make_shard(X, metric_id, lo) as shard:
+        if warm:
+            shard.set_state(d0, a0.astype(np.int32))
+        else:
+            # util.assign_to_nearest_center (util.py:199-203) to the medoids' rows
+            d = np.full(hi - lo, np.inf, dtype=np.float64)
+            a = np.zeros(hi - lo, dtype=np.int32)
+            for i, c in enumerate(rows_of(med)):
+                dc = shard.distance(np.asarray(c))
+                closer = dc < d
+                d[closer] = dc[closer]
+                a[closer] = i
+            shard.set_state(d, a)
+        for _ in range(int(n_iters)):
+            med = pam_sweep_sharded(shard, med, proposals=prop, random_state=rs,
+                                    group=group)
+        d, a = shard.state()
+    pairs = []
+    for g in med:
+        r = int(np.searchsorted(starts, g, side="right") - 1)
+        pairs.append((r, int(g - starts[r])))
+    return util.ClusterResult(
+        center_indices=pairs, assignments=np.asarray(a).astype(np.int64),
+        distances=np.asarray(d, dtype=np.float64), centers=rows_of(med))

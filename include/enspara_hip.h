@@ -649,6 +649,56 @@ int ek_feat_pam_sweep(ek_feat *k, int32_t metric, int32_t n_medoids, int64_t *me
                       int32_t *accept, int32_t *cid, int32_t *status);
 /* frees what ek_feat_pam_sweep keeps between calls (ek_feat_destroy does it too) */
 void ek_feat_pam_release(ek_feat *k);
+/* ---- the same sweep over several shards (one ek_feat handle each) --------------
+ * The reference's MPI branch of the sweep (kmedoids.py:575-699 with the draw of
+ * :482-517) for a feature metric, on handles made by ek_feat_create_sharded that
+ * hold a state (a k-centers run, ek_feat_state_reset / _upload).  The float64
+ * distances, the labels and the features of ALL medoids stay on every shard; the
+ * caller keeps the random stream and the decision.  Protocol, per sweep:
+ *   1. every shard gathers the rows of the medoids it owns into a table
+ *      [n_medoids][n_features] in the samples' element kind, zero elsewhere
+ *      (ek_feat_pam_gather_rows: samples_host are LOCAL indices, rows_host the
+ *      table rows they go to -- the library does not know the table's height:
+ *      the caller guarantees rows_host[i] < its rows); the caller adds the shards' tables up (each row has
+ *      one owner) and hands the sum to ek_feat_pam_begin, which keeps its own copy;
+ *   2. per window of clusters (at most 32 per call, the limit of this interface;
+ *      the driver in enspara_amd/sharded.py uses windows of 8):
+ *      ek_feat_pam_count_batch -> the local member
+ *      counts of clusters cid0 .. cid0 + count - 1 (the caller gathers them and
+ *      draws choice(m) over the global count, members in global order);
+ *      ek_feat_pam_select_batch(js) -> the js[j]-th LOCAL member of cluster
+ *      cid0 + j in local order (-1 where js[j] < 0), from the scans the count of
+ *      the same cid0 left; the owners gather the proposals' rows as in 1.;
+ *   3. per proposal ek_feat_pam_propose(cid, row_dev, win_lo, win_count, out_dev):
+ *      ONE read of the shard's samples -- metric(X_local, row) with the arithmetic
+ *      of ek_feat_distance, the three masks of kmedoids.py:644-658 into a trial
+ *      state, the ambiguous members against all medoids with the row in place of
+ *      medoid cid (strict <, ascending medoid index) -- then the record at out_dev
+ *        { double sum_old, sum_new; int64_t n; uint32_t n_amb, moved }   (32 bytes)
+ *      sum_old / sum_new = np.sum(d ** 2) of the shard's distances as they stand /
+ *      as the proposal would leave them, each in numpy's pairwise order over the
+ *      shard's own float64 array; n = the shard's samples; n_amb = its ambiguous
+ *      members; moved bit i = cluster win_lo + i (i < win_count <= 32) would lose
+ *      or gain a sample on this shard.  A shard without samples writes zeros.
+ *      The caller exchanges the records (one all-gather), adds the sums in shard
+ *      order, divides by the global sample count and accepts iff new < old (:683);
+ *   4. ek_feat_pam_commit(accept) on every shard: the trial state becomes the
+ *      state, or the medoid table gets its column back.  One proposal at a time.
+ * Nothing per sample crosses to the host.  All launches go to the handle's stream;
+ * count / select / gather wait for it, begin / propose / commit do not.  With one
+ * shard holding every sample the state after a sweep is ek_feat_pam_sweep's, bit
+ * for bit. */
+int ek_feat_pam_count_batch(ek_feat *k, int32_t cid0, int32_t count,
+                            int64_t *counts_host);
+int ek_feat_pam_select_batch(ek_feat *k, int32_t cid0, int32_t count,
+                             const int64_t *js_host, int64_t *members_host);
+int ek_feat_pam_gather_rows(ek_feat *k, int32_t count, const int64_t *samples_host,
+                            const int64_t *rows_host, void *table_dev);
+int ek_feat_pam_begin(ek_feat *k, int32_t metric, const void *table_dev,
+                      int32_t n_medoids);
+int ek_feat_pam_propose(ek_feat *k, int32_t cid, const void *row_dev, int32_t win_lo,
+                        int32_t win_count, void *out_dev);
+int ek_feat_pam_commit(ek_feat *k, int32_t accept);
 
 /* ---- tuning knobs (benchmarks only) -------------------------------------- */
 /* frames per lane of the distance kernel: 1, 2 or 4; 0 = choose from the

@@ -55,6 +55,7 @@ SYMBOLS = [
     "ek_feat_kcenters_step", "ek_feat_history_download", "ek_feat_history_reset",
     "ek_feat_pam_count_batch", "ek_feat_pam_select_batch", "ek_feat_pam_gather_rows",
     "ek_feat_pam_begin", "ek_feat_pam_propose", "ek_feat_pam_commit",
+    "ek_feat_assign_nearest",
     "ek_set_frames_per_lane", "ek_set_option", "ek_get_option", "ek_last_run_timing",
     "ek_reserve_centers",
     "ek_debug_guards",
@@ -245,6 +246,7 @@ def load():
     L.ek_feat_pam_begin.argtypes = [vp, i32, vp, i32]
     L.ek_feat_pam_propose.argtypes = [vp, i32, vp, i32, i32, vp]
     L.ek_feat_pam_commit.argtypes = [vp, i32]
+    L.ek_feat_assign_nearest.argtypes = [vp, i32, vp, i32]
     L.ek_set_frames_per_lane.argtypes = [vp, C.c_int]
     L.ek_set_option.argtypes = [vp, i32, i32]
     L.ek_get_option.argtypes = [vp, i32, i32p]

@@ -117,3 +117,57 @@ def reassign(trajectories, centers, frac_mem=0.5, device=0, batch_size=None):
     if all(len(assignments[0]) == len(a) for a in assignments):
         return np.array(assignments), np.array(distances)
     return ra.RaggedArray(assignments), ra.RaggedArray(distances)
+
+
+def reassign_features(arrays, centers, metric, batch_size=None, frac_mem=0.5,
+                      device=0):
+    """:func:`reassign` for feature data: every row of every array ``[L_i, F]``
+    (or zero-argument callable returning one) is assigned to the nearest of
+    ``centers`` ``[K, F]`` under ``metric`` ('euclidean', 'manhattan' /
+    'cityblock' or one of the libdist callables).  Consecutive arrays are packed
+    into batches (:func:`compute_batches`), a batch is one upload and one launch
+    of the nearest-center scan (libdist.assign_nearest_resident): the labels and
+    float64 distances util.assign_to_nearest_center gives per array.  Returns
+    (assignments, distances) as ndarrays when all arrays have the same length
+    and as RaggedArrays otherwise."""
+    from ..geometry import libdist
+    method = util._get_distance_method(metric)
+    metric_id = getattr(method, "device_metric_id", None)
+    if metric_id is None:
+        raise ImproperlyConfigured(
+            "reassign_features needs a libdist metric ('euclidean', "
+            "'manhattan' or libdist.hamming), got %r" % (metric,))
+    loaded = [np.asarray(t() if callable(t) else t) for t in arrays]
+    for x in loaded:
+        if x.ndim != 2 or x.shape[1] != loaded[0].shape[1]:
+            raise ImproperlyConfigured(
+                "reassign_features needs arrays of shape [L_i, F] with one F, "
+                "got %s" % ([x.shape for x in loaded],))
+    if not loaded:
+        return np.zeros((0, 0), dtype=np.int64), np.zeros((0, 0))
+    lengths = [len(x) for x in loaded]
+    F = loaded[0].shape[1]
+    if batch_size is None:
+        import torch
+        _, total = torch.cuda.mem_get_info(device)
+        # staging + tiles in at most 8 bytes per element, float64 / int32 state
+        batch_size = int(total * frac_mem / (F * 8 * 2 + 16))
+        logger.info("Batch max size set to %s samples.", batch_size)
+    if batch_size < max(lengths):
+        raise ImproperlyConfigured(
+            'Batch size of %s was smaller than largest array (size %s).' %
+            (batch_size, max(lengths)))
+    assignments, distances = [], []
+    for idx in compute_batches(lengths, batch_size):
+        blens = [lengths[i] for i in idx]
+        if sum(blens) == 0:
+            a, d = np.zeros(0, dtype=np.int64), np.zeros(0)
+        else:
+            a, d = libdist.assign_nearest_resident(
+                np.concatenate([loaded[i] for i in idx]), metric_id, centers,
+                device)
+        assignments.extend(ra.partition_list(a, blens))
+        distances.extend(ra.partition_list(d, blens))
+    if all(n == lengths[0] for n in lengths):
+        return np.array(assignments), np.array(distances)
+    return ra.RaggedArray(assignments), ra.RaggedArray(distances)

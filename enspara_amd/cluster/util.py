@@ -100,6 +100,29 @@ def _stack_centers(cluster_centers):
     return np.concatenate(rows, axis=0)
 
 
+def _feature_scan_applies(trajectory, cluster_centers, distance_method):
+    """the device form of the scan below: a libdist metric, a non-empty 2-D
+    array of real numbers (not float16), centers that stack to [K, F]"""
+    if getattr(distance_method, "device_metric_id", None) is None:
+        return False
+    X = trajectory
+    if not (isinstance(X, np.ndarray) and X.ndim == 2 and X.shape[0] > 0
+            and X.dtype.kind in "fiu" and X.dtype != np.float16):
+        return False
+    if hasattr(cluster_centers, "xyz"):
+        return False
+    if isinstance(cluster_centers, np.ndarray):
+        rows = [cluster_centers] if cluster_centers.ndim == 2 else []
+    else:
+        try:
+            rows = [np.asarray(c)[None] for c in cluster_centers]
+        except (TypeError, ValueError):
+            return False
+    return bool(rows) and all(
+        r.ndim == 2 and r.shape[1] == X.shape[1] and r.dtype.kind in "fiu"
+        for r in rows)
+
+
 def assign_to_nearest_center(trajectory, cluster_centers, distance_method):
     """reference util.py:159-205.  Returns (assignments int64, distances
     float64).  Lowest center index wins ties (strict <)."""
@@ -117,6 +140,16 @@ def assign_to_nearest_center(trajectory, cluster_centers, distance_method):
             if own:
                 store.close()
         return a.astype(np.int64), d.astype(np.float64)
+
+    if _feature_scan_applies(trajectory, cluster_centers, distance_method):
+        # a libdist metric: the whole scan is one launch (ek_feat_assign_nearest)
+        from ..geometry import libdist
+        if (isinstance(distance_method, libdist.Bound)
+                and distance_method.X is trajectory):
+            return distance_method.assign_nearest(cluster_centers)
+        return libdist.assign_nearest_resident(
+            trajectory, distance_method.device_metric_id, cluster_centers,
+            getattr(distance_method, "device", 0))
 
     if hasattr(distance_method, "bind"):     # device metric: upload once
         distance_method = distance_method.bind(trajectory)

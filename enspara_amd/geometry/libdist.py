@@ -50,6 +50,7 @@ class _Resident:
     def __init__(self, Xc, kind, device):
         self.L = _lib.load()
         self.kind = kind
+        self.n = int(Xc.shape[0])
         h = C.c_void_p()
         _lib.check(self.L.ek_feat_create(int(device), Xc.shape[0], Xc.shape[1],
                                          kind, C.byref(h)))
@@ -73,6 +74,22 @@ class _Resident:
             _lib.f64p(dist), _lib.i32p(assign), _lib.i64p(centers), C.byref(k),
             C.byref(fmax)))
         return centers[:k.value].copy(), fmax.value
+
+    def assign_nearest(self, metric, centers):
+        """ek_feat_assign_nearest: every sample against ``centers`` ([K, F] in
+        this matrix's working dtype) in one launch; the result is the handle's
+        resident state.  -> (distances float64 [n], labels int32 [n])"""
+        n = int(self.n)
+        cc = np.ascontiguousarray(centers)
+        _lib.check(self.L.ek_feat_assign_nearest(
+            self._h, int(metric),
+            cc.ctypes.data_as(C.c_void_p) if len(cc) else None, len(cc)))
+        d = np.empty(n, dtype=np.float64)
+        a = np.empty(n, dtype=np.int32)
+        if n:
+            _lib.check(self.L.ek_feat_state_download(self._h, _lib.f64p(d),
+                                                     _lib.i32p(a)))
+        return d, a
 
     def pam_sweep(self, metric, medoids, proposals, raw, pos, dist, assign, accept,
                   cid):
@@ -137,6 +154,15 @@ class FeatureStore(_Resident):
                               "array dimension (%s)" % (y.shape, self.F))
         if self.n:
             super().distance(metric, y, out)
+
+    def assign_nearest(self, metric, centers):
+        """every local sample against ``centers`` ([K, F], any dtype) in one
+        launch on this store's stream; the state on the device becomes the
+        result (lowest index among equal distances, label 0 / +inf where no
+        distance is below +inf), ready for ``local_candidate`` /
+        ``kcenters_step``.  -> (distances float64 [n], labels int32 [n])"""
+        c = _centers_array(centers, self.F, self.dtype)
+        return super().assign_nearest(metric, c)
 
     @classmethod
     def from_array(cls, X, metric, device=0, global_offset=0, stream=None):
@@ -253,6 +279,19 @@ def _working_dtype(X, hamming):
     return np.float64
 
 
+def _centers_array(centers, F, dt):
+    """centers -> contiguous [K, F] in the working dtype (as ``y`` is converted)"""
+    if isinstance(centers, np.ndarray):
+        c = centers
+    else:                   # row by row, as the per-center loop converts them
+        rows = [np.ascontiguousarray(r, dtype=dt) for r in centers]
+        c = np.stack(rows) if rows else np.zeros((0, F), dtype=dt)
+    if c.ndim != 2 or c.shape[1] != F:
+        raise DataInvalid("Cluster centers of shape %s do not match data array "
+                          "dimension (%s)" % (c.shape, F))
+    return np.ascontiguousarray(c, dtype=dt)
+
+
 class Bound:
     """``metric`` bound to one sample matrix that stays resident on the GPU:
     ``bound(X, y)`` costs one kernel and one read-back when ``X`` is the bound
@@ -278,6 +317,18 @@ class Bound:
         if X is self.X and (device is None or device == self.device):
             return self
         return Bound(self.metric, X, self.device if device is None else device)
+
+    def assign_nearest(self, centers):
+        """the nearest of ``centers`` for every row of the bound matrix, one
+        launch (:func:`assign_nearest_resident` without the upload of X)
+        -> (assignments int64, distances float64)"""
+        if self.res is None:
+            return assign_nearest_resident(self.X, self.metric, centers,
+                                           self.device)
+        Xa = np.asarray(self.X)
+        d, a = self.res.assign_nearest(
+            self.metric, _centers_array(centers, Xa.shape[1], self.dt))
+        return a.astype(np.int64), d
 
     def __call__(self, X, y, out=None):
         if X is not self.X or self.res is None:
@@ -348,3 +399,24 @@ def kcenters_resident(X, metric_id, first_label, max_new, cutoff, distances,
     a = np.ascontiguousarray(assignments, dtype=np.int32).copy()
     centers, fmax = res.kcenters(metric_id, first_label, max_new, cutoff, d, a)
     return centers, d, a.astype(np.asarray(assignments).dtype), fmax
+
+
+def assign_nearest_resident(X, metric_id, centers, device=0):
+    """The nearest-center scan (reference util.py:186-203) for one of the
+    metrics above in one launch, X resident on the device: label 0 and +inf to
+    begin with, the centers in ascending order, strict < -- the values and
+    labels the per-center loop gives, bit for bit.  ``centers``: [K, F], converted
+    to the working dtype as ``y`` is.  Returns (assignments int64, distances
+    float64).  Counterpart of :func:`kcenters_resident`."""
+    Xa = np.asarray(X)
+    if Xa.ndim != 2:
+        raise DataInvalid(
+            "Data array dimension must be two, got shape %s." % str(Xa.shape))
+    dt = _working_dtype(Xa, metric_id == 2)
+    c = _centers_array(centers, Xa.shape[1], dt)
+    if Xa.shape[0] == 0:
+        return np.zeros(0, dtype=np.int64), np.full(0, np.inf)
+    res = _Resident(np.ascontiguousarray(Xa, dtype=dt),
+                    _KIND[np.dtype(dt).name], device)
+    d, a = res.assign_nearest(metric_id, c)
+    return a.astype(np.int64), d

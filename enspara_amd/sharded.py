@@ -306,6 +306,12 @@ class FeatureShard:
         self.store.distance(self.metric, y, out)
         return out
 
+    def assign_nearest(self, centers):
+        """the nearest of ``centers`` ([K, n_features] rows) for every local
+        sample, one launch; the result is the state on the device
+        -> (distances float64 [n_local], labels int32 [n_local]) on the host"""
+        return self.store.assign_nearest(self.metric, centers)
+
     def reset_state(self):
         """distances +inf, labels -1"""
         self.store.reset_state()
@@ -1315,6 +1321,26 @@ def _feature_data_problem(X, metric_id):
     return None
 
 
+def _assign_shard_to_centers(shard, centers, n_local):
+    """util.assign_to_nearest_center (util.py:199-203) of the shard's samples
+    to ``centers`` as the shard's state: label 0 / +inf, then every center in
+    order, strict <.  A device shard does the scan in one launch and keeps the
+    result where the steps that follow read it; a shard object without
+    ``assign_nearest`` gets the per-center loop around its ``distance``.
+    -> (distances float64, labels int32) on the host"""
+    if hasattr(shard, "assign_nearest"):
+        return shard.assign_nearest(centers)
+    d = np.full(n_local, np.inf, dtype=np.float64)
+    a = np.zeros(n_local, dtype=np.int32)
+    for i, c in enumerate(centers):
+        dc = shard.distance(np.asarray(c))
+        closer = dc < d
+        d[closer] = dc[closer]
+        a[closer] = i
+    shard.set_state(d, a)
+    return d, a
+
+
 def _device_feature_shard(Xw, metric_id, offset):
     """The product's shard: a FeatureStore on a torch stream of its own on the
     current CUDA device, the driver running under that stream."""
@@ -1464,16 +1490,7 @@ def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
             shard.reset_state()
         else:
             centers = [c for c in init_centers]
-            # util.assign_to_nearest_center (util.py:199-203): label 0 / +inf,
-            # then every center in order, strict <
-            d = np.full(hi - lo, np.inf, dtype=np.float64)
-            a = np.zeros(hi - lo, dtype=np.int32)
-            for i, c in enumerate(centers):
-                dc = shard.distance(np.asarray(c))
-                closer = dc < d
-                d[closer] = dc[closer]
-                a[closer] = i
-            shard.set_state(d, a)
+            d, a = _assign_shard_to_centers(shard, centers, hi - lo)
             med = _closest_members(d, a, lo, len(centers), group)
         budget = (np.inf if n_clusters is None else n_clusters) - len(med)
         max_new = (0 if budget <= 0 else
@@ -1651,15 +1668,7 @@ def kmedoids_features_sharded(X, metric_id, n_clusters=None, n_iters=5,
         if warm:
             shard.set_state(d0, a0.astype(np.int32))
         else:
-            # util.assign_to_nearest_center (util.py:199-203) to the medoids' rows
-            d = np.full(hi - lo, np.inf, dtype=np.float64)
-            a = np.zeros(hi - lo, dtype=np.int32)
-            for i, c in enumerate(rows_of(med)):
-                dc = shard.distance(np.asarray(c))
-                closer = dc < d
-                d[closer] = dc[closer]
-                a[closer] = i
-            shard.set_state(d, a)
+            _assign_shard_to_centers(shard, rows_of(med), hi - lo)
         for _ in range(int(n_iters)):
             med = pam_sweep_sharded(shard, med, proposals=prop, random_state=rs,
                                     group=group)

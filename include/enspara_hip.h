@@ -622,6 +622,20 @@ int ek_feat_history_download(ek_feat *k, int32_t first, int32_t count,
                              int64_t *center_index_out, double *center_dist_out,
                              int32_t *n_done);
 int ek_feat_history_reset(ek_feat *k);
+/* Every sample against a table of centers (reference util.py:186-203 around a
+ * libdist metric): centers_host is row-major [n_centers][n_features] in the
+ * handle's element kind.  One launch: label 0 and distance +inf to begin with,
+ * the centers visited in ascending order, updated on strict < (NaN is never
+ * taken, the lowest index wins ties); every (sample, center) distance is one
+ * thread's sum over the features in order, the arithmetic of ek_feat_distance,
+ * so labels and float64 distances are what n_centers calls of it and the host
+ * scan give, bit for bit.  The result replaces the handle's resident state
+ * (float64 distances, int32 labels: ek_feat_state_download, ek_feat_kcenters_step
+ * continue from it); n_centers == 0 leaves label 0 / +inf.  Works on handles of
+ * ek_feat_create and ek_feat_create_sharded (on the caller's stream there);
+ * returns after the work has completed. */
+int ek_feat_assign_nearest(ek_feat *k, int32_t metric, const void *centers_host,
+                           int32_t n_centers);
 /* One PAM sweep (reference kmedoids.py:575-699, serial branch) over clusters
  * *cid .. n_medoids - 1 for metric 0 (euclidean) / 1 (manhattan), with the
  * float64 distances, the labels and the medoids' features resident on the device:

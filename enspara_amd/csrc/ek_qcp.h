@@ -96,11 +96,12 @@ __device__ __forceinline__ double ek_msd_from_S(const float (&S)[9], double Gx,
                                                 double Gy, int n_atoms)
 {
     const EkQuartic p = ek_quartic_from_S(S);
-    const double C2 = p.C2, C1 = p.C1, C0 = p.C0;
+    const double q = p.q, C2 = p.C2, C1 = p.C1, C0 = p.C0;
 
     // largest root of l^4 + C2 l^2 + C1 l + C0 by Newton from the upper bound
     const double Gsum = Gx + Gy;
-    double lam = 0.5 * Gsum;
+    const double top = 0.5 * Gsum;
+    double lam = top;
     for (int it = 0; it < EK_MAXIT; ++it) {
         const double x2 = lam * lam;
         const double b = (x2 + C2) * lam;
@@ -110,7 +111,15 @@ __device__ __forceinline__ double ek_msd_from_S(const float (&S)[9], double Gx,
         if (den == 0.0)
             break;
         const double delta = num / den;
-        lam = lam - delta;
+        const double nxt = lam - delta;
+        // the largest root lies in [sqrt(q / 3), (Gx + Gy) / 2] (it is at least
+        // the largest singular value of S) and in exact arithmetic so does every
+        // iterate: a step out of it is noise divided by noise at a multiple root
+        // (a rank-one S against itself: (l^2 - s1^2)^2, started AT the root), and
+        // the iterate stays where it was
+        if (!(nxt > 0.0 && nxt <= top && 3.0 * (nxt * nxt) >= q))
+            break;
+        lam = nxt;
         if (__builtin_fabs(delta) < __builtin_fabs(EK_EVALPREC * lam))
             break;
     }
@@ -410,7 +419,8 @@ __device__ __forceinline__ float ek_rmsd_from_S_below(const float (&S)[9],
                 return __builtin_inff();
         }
     }
-    double lam = 0.5 * Gsum;
+    const double top = 0.5 * Gsum;
+    double lam = top;
     for (int it = 0; it < EK_MAXIT; ++it) {
         const double x2 = lam * lam;
         const double b = (x2 + C2) * lam;
@@ -420,7 +430,11 @@ __device__ __forceinline__ float ek_rmsd_from_S_below(const float (&S)[9],
         if (den == 0.0)
             break;
         const double delta = num / den;
-        lam = lam - delta;
+        const double nxt = lam - delta;
+        // (the step rule of ek_msd_from_S)
+        if (!(nxt > 0.0 && nxt <= top && 3.0 * (nxt * nxt) >= q))
+            break;
+        lam = nxt;
         if (__builtin_fabs(delta) < __builtin_fabs(EK_EVALPREC * lam))
             break;
         if (Gsum - 2.0 * lam > far)

@@ -37,7 +37,9 @@
  *   - S_ij = sum_a x_ai * y_aj accumulated in float32 with one fused
  *     multiply-add per term, sequentially in atom order (x = frame, y = center);
  *   - quartic coefficients and Newton iteration in float64, no contraction
- *     (build with -ffp-contract=off), explicit fma() only where written;
+ *     (build with -ffp-contract=off), explicit fma() only where written; the
+ *     iteration stops before a step that would leave [sqrt(q/3), (G_x+G_y)/2],
+ *     q = sum S_ij^2 (a multiple largest root: rank-one S against itself);
  *   - rmsd = sqrtf((float)max(0, msd)).
  */
 #include <math.h>
@@ -131,7 +133,8 @@ double eko_msd_from_S(const float S[9], double Gx, double Gy, int n_atoms)
     C0 = C0 + s5 * c0;
 
     const double Gsum = Gx + Gy;
-    double lam = 0.5 * Gsum;
+    const double top = 0.5 * Gsum;
+    double lam = top;
     for (int it = 0; it < EKO_MAXIT; ++it) {
         const double x2 = lam * lam;
         const double b = (x2 + C2) * lam;
@@ -141,7 +144,14 @@ double eko_msd_from_S(const float S[9], double Gx, double Gy, int n_atoms)
         if (den == 0.0)
             break;
         const double delta = num / den;
-        lam = lam - delta;
+        const double nxt = lam - delta;
+        /* the largest root lies in [sqrt(q / 3), (Gx + Gy) / 2] (it is at
+         * least the largest singular value of S) and in exact arithmetic so
+         * does every iterate: a step out of it is noise divided by noise at a
+         * multiple root, and the iterate stays where it was */
+        if (!(nxt > 0.0 && nxt <= top && 3.0 * (nxt * nxt) >= q))
+            break;
+        lam = nxt;
         if (fabs(delta) < fabs(EKO_EVALPREC * lam))
             break;
     }

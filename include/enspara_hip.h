@@ -503,6 +503,30 @@ int ek_msm_counts_ctx(ek_ctx *ctx, const int64_t *lengths, int64_t n_trj,
  * NULL. */
 int ek_msm_row_normalize(int device, const int64_t *indptr, const double *data,
                          int64_t n_rows, double *probs_out, double *rowsum_out);
+/* ek_msm_mle_prinz replaces the iteration of builders.mle
+ * (enspara/msm/builders.py:215-318): Prinz's reversible maximum-likelihood
+ * sweeps over n states, all of them in one launch.  All arrays are host
+ * memory.  The off-diagonal pairs i < j to update (those with
+ * C[i,j] + C[j,i] > 0) are given level-major: level l holds pairs
+ * [level_ptr[l], level_ptr[l+1]), no two pairs of a level share a state, and
+ * two pairs that share a state lie in levels ordered as the pairs are
+ * lexicographically -- then the result is the lexicographic sweep's bit for
+ * bit (enspara_amd/msm/builders.py builds the levels; the call checks the
+ * indices and the first property and returns EK_EARG otherwise).
+ * c_ij[p] = C[i,j], c_ji[p] = C[j,i]; c_diag[s] = C[s,s]; c_rs = row sums of C.
+ * x_pairs (X[i,j] = X[j,i]), x_diag, x_rs (row sums of X) hold X = C + C^T on
+ * entry and the iterate on return.  A sweep is followed by another while
+ * |logl - logl of the sweep before| > tol (0 before the first), at most
+ * max_iter >= 1 sweeps: a negative tol runs exactly max_iter.  *n_iter_out =
+ * sweeps that ran, *logl_out = logl of the last (the reference's formula,
+ * :266 and :296-299, summed in a fixed order of the device's own). */
+int ek_msm_mle_prinz(int device, int32_t n, int64_t n_pairs, int32_t n_levels,
+                     const int64_t *level_ptr, const int32_t *pair_i,
+                     const int32_t *pair_j, const double *c_ij,
+                     const double *c_ji, const double *c_diag,
+                     const double *c_rs, double *x_pairs, double *x_diag,
+                     double *x_rs, double tol, int64_t max_iter,
+                     int64_t *n_iter_out, double *logl_out);
 
 /* ---- leading eigenpairs of a sparse transition matrix ---------------------------
  * Device primitives of an Arnoldi / Krylov-Schur solver replacing the ARPACK /

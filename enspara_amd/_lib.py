@@ -45,7 +45,7 @@ SYMBOLS = [
     "ek_centered_frames", "ek_pam_begin_table", "ek_pam_prefetch_centers",
     "ek_pam_propose_center",
     "ek_msm_counts", "ek_msm_counts_ctx", "ek_msm_row_normalize",
-    "ek_msm_mle_prinz",
+    "ek_msm_mle_prinz", "ek_msm_bace_prune", "ek_msm_bace_run",
     "ek_krylov_create", "ek_krylov_destroy", "ek_krylov_set_vector",
     "ek_krylov_get_vector", "ek_krylov_step", "ek_krylov_rotate",
     "ek_krylov_combine", "ek_krylov_expand", "ek_krylov_set_filter",
@@ -213,6 +213,9 @@ def load():
     L.ek_msm_mle_prinz.argtypes = [C.c_int, i32, i64, i32, i64p, i32p, i32p, f64p,
                                    f64p, f64p, f64p, f64p, f64p, f64p, C.c_double,
                                    i64, i64p, f64p]
+    L.ek_msm_bace_prune.argtypes = [C.c_int, i32, f64p, f64p, f32p]
+    L.ek_msm_bace_run.argtypes = [C.c_int, i32, f64p, f64p, i32p, i32, i32, i32, vp,
+                                  i32, f32p]
     L.ek_krylov_create.argtypes = [C.c_int, i64, i64p, i32p, f64p, i32,
                                    C.POINTER(vp)]
     L.ek_krylov_destroy.argtypes = [vp]

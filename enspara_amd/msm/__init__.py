@@ -6,3 +6,4 @@ from .transition_matrices import assigns_to_counts, eigenspectrum, eq_probs  # n
 from .msm import MSM  # noqa: F401
 from .timescales import implied_timescales  # noqa: F401
 from .trimming import TrimMapping, trim_disconnected  # noqa: F401
+from . import bace  # noqa: F401  (a module, as in the reference: msm.bace.bace)

@@ -527,6 +527,32 @@ int ek_msm_mle_prinz(int device, int32_t n, int64_t n_pairs, int32_t n_levels,
                      const double *c_rs, double *x_pairs, double *x_diag,
                      double *x_rs, double tol, int64_t max_iter,
                      int64_t *n_iter_out, double *logl_out);
+/* BACE coarse-graining (enspara/msm/bace.py; Bowman, J. Chem. Phys. 137, 134111
+ * (2012)).  All arrays are host memory; c is dense, row-major [n][n], finite and
+ * not negative, n at most 16384.
+ * ek_msm_bace_prune replaces the Bayes factors of baysean_prune (:341-369):
+ * d_out[s] = the float32 value of state s against the pseudo-state
+ * (multiDistHelper with c1 = float32(1) / float32(n), w1 = 1, c2 = c[s, :] +
+ * 1 / n, w2 = w[s]), the sum taken in float64. */
+int ek_msm_bace_prune(int device, int32_t n, const double *c, const double *w,
+                      float *d_out);
+/* ek_msm_bace_run replaces calcDMat and mergeTwoClosestStates (:122-213): the
+ * initial matrix of inverse Bayes factors over the pairs s < d, s kept,
+ * c[s, d] > 1, then n_merges merges, each followed by the recomputation of row
+ * minX and the arg-max of the whole float32 matrix (first row-major index on
+ * ties), without a host round trip in between.  c: the pruned counts; w: their
+ * row sums + 1 on kept states; kept[n_kept]: the kept states, increasing;
+ * n_merges must be max(n_kept - n_macrostates, 0).  records_out: n_merges + 1
+ * records of 16 bytes { int32 minX, int32 minY, float32 1 / dMat[minX, minY],
+ * int32 status }, one for the initial matrix and one after every merge; status 0:
+ * a pair, 1: no pair with c > 1 was left (the matrix's maximum is 0: the factor
+ * is 1 / 0 and nothing is merged after it), 2: not run for that reason.
+ * dmat_steps > 0 (tests): dmat_out[step][n][n] receives the matrix as steps
+ * 0 .. dmat_steps - 1 leave it. */
+int ek_msm_bace_run(int device, int32_t n, const double *c, const double *w,
+                    const int32_t *kept, int32_t n_kept, int32_t n_macrostates,
+                    int32_t n_merges, void *records_out, int32_t dmat_steps,
+                    float *dmat_out);
 
 /* ---- leading eigenpairs of a sparse transition matrix ---------------------------
  * Device primitives of an Arnoldi / Krylov-Schur solver replacing the ARPACK /

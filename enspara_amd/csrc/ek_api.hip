@@ -1,5 +1,7 @@
 // ek_api.hip -- the C ABI of include/enspara_hip.h (host side).
 #include "ek_ctx.h"
+#include "ek_view.h"
+#include <cmath>
 #include <mutex>
 #include "ek_qcp.h"
 
@@ -366,6 +368,7 @@ int ek_free_all(ek_ctx *c)
     if (c->win_ev)
         (void)hipEventDestroy(c->win_ev);
     (void)hipFree(c->fm);
+    ek_view_free(c);
     (void)hipFree(c->top);
     (void)hipFree(c->planD);
     (void)hipFree(c->ndist);
@@ -638,6 +641,12 @@ extern "C" int ek_set_option(ek_ctx *c, int32_t key, int32_t value)
                                     "(by the shard's size) or 2 (always)");
         c->pass_sweep = value;
         return EK_OK;
+    case EK_OPT_ACTIVE_VIEW:
+        if (value < 0 || value > 2)
+            return ek_fail(EK_EARG, "ek_set_option: active view 0 (never), 1 (by the "
+                                    "policy) or 2 (forced)");
+        c->active_view = value;
+        return EK_OK;
     case EK_OPT_ASSIGN_KERNEL:
         if (value < 0 || value > 3)
             return ek_fail(EK_EARG, "ek_set_option: assign variant 0..3");
@@ -675,6 +684,7 @@ extern "C" int ek_get_option(ek_ctx *c, int32_t key, int32_t *value)
     case EK_OPT_PAM_AHEAD: *value = c->pam_spec; return EK_OK;
     case EK_OPT_PAM_ZERO_COPY: *value = c->pam_zero_copy; return EK_OK;
     case EK_OPT_PAM_PAIRS_MFMA: *value = ek_pam_pairs_form; return EK_OK;
+    case EK_OPT_ACTIVE_VIEW: *value = c->active_view; return EK_OK;
     default:
         return ek_fail(EK_EARG, "ek_get_option: unknown key %d", key);
     }
@@ -1105,10 +1115,125 @@ extern "C" int ek_history_download(ek_ctx *c, int32_t first, int32_t count,
 // produce the same centers, labels and distances, so the choice is free: every
 // batch is timed on the device (centers per millisecond) and the other form is
 // tried for a short batch at intervals that double while it keeps losing.
+// ---- the active view (ek_view.hip; DESIGN.md 4a "Active view") ---------------------
+// The policy's two constants: a view's guard sits at EK_VIEW_RHO x the maximum it was
+// built at (frames at up to about half of that are settled), and a view is built when
+// it would stream at most EK_VIEW_SHRINK x the frames streamed now.
+static constexpr double EK_VIEW_RHO = 0.75;
+static constexpr double EK_VIEW_SHRINK = 0.8;
+static constexpr int EK_VIEW_MIN_ROUNDS = 24;   // rounds left that make a rebuild worth it
+static constexpr int EK_VIEW_BATCH = 16;        // rounds between two looks at the policy
+static constexpr double EK_VIEW_REL = 1e-3, EK_VIEW_ABS = 1e-3;     // ek_round_ti_*'s margin
+
+void ek_view_free(ek_ctx *c)
+{
+    (void)hipFree(c->v_aos);
+    (void)hipFree(c->v_tiles);
+    (void)hipFree(c->v_qtiles);
+    (void)hipFree(c->v_G);
+    (void)hipFree(c->v_dist);
+    (void)hipFree(c->v_assign);
+    (void)hipFree(c->v_act);
+    (void)hipFree(c->v_blockcnt);
+    (void)hipFree(c->v_blockoff);
+    (void)hipFree(c->v_count);
+    c->v_aos = c->v_tiles = c->v_qtiles = nullptr;
+    c->v_G = nullptr;
+    c->v_dist = nullptr;
+    c->v_assign = nullptr;
+    c->v_act = c->v_blockcnt = c->v_blockoff = c->v_count = nullptr;
+    c->view_cap = 0;
+}
+
+// room for a view of `frames` frames (whole tiles); EK_ENOMEM: there is none, and the
+// context remembers
+static int ek_view_alloc(ek_ctx *c, int64_t frames)
+{
+    const int64_t cap = (frames + EK_TILE - 1) / EK_TILE * EK_TILE;
+    if (c->view_cap >= cap)
+        return EK_OK;
+    EK_HIP(ek_wait(c));
+    ek_view_free(c);
+    const size_t nt = (size_t)(cap / EK_TILE), A3 = (size_t)3 * c->A;
+    const size_t nblk = ek_view_sel_blocks(std::max<int64_t>(c->n, 1));
+    hipError_t e = hipSuccess;
+#define EK_VALLOC(ptr, bytes)                                                  \
+    if (e == hipSuccess)                                                       \
+        e = ek_malloc_named(c, (void **)&(ptr), (bytes), #ptr);
+    EK_VALLOC(c->v_aos, (size_t)cap * A3 * sizeof(float));
+    EK_VALLOC(c->v_tiles, nt * A3 * EK_TILE * sizeof(float));
+    EK_VALLOC(c->v_qtiles, ek_quad_tiles_bytes((int64_t)nt, c->A));
+    EK_VALLOC(c->v_G, (size_t)cap * sizeof(double));
+    EK_VALLOC(c->v_dist, (size_t)cap * sizeof(float));
+    EK_VALLOC(c->v_assign, (size_t)cap * sizeof(int32_t));
+    EK_VALLOC(c->v_act, (size_t)cap * sizeof(uint32_t));
+    EK_VALLOC(c->v_blockcnt, nblk * sizeof(uint32_t));
+    EK_VALLOC(c->v_blockoff, nblk * sizeof(uint32_t));
+    EK_VALLOC(c->v_count, 2 * sizeof(uint32_t));
+#undef EK_VALLOC
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ek_view_free(c);
+        if (e == hipErrorOutOfMemory) {
+            c->view_nomem = true;
+            return EK_ENOMEM;
+        }
+        EK_HIP(e);
+    }
+    c->view_cap = cap;
+    return EK_OK;
+}
+
+// the store the rounds see: the shard's own, or its active view
+struct EkStore {
+    float *dist;
+    int32_t *assign;
+    const float *tiles, *qtiles, *aos;
+    const double *G;
+    int64_t n, n_pad;
+};
+// a run's view, for the one who has to put it back
+struct EkViewRun {
+    bool on = false;
+    int64_t n = 0;              // frames in it
+    int32_t label_lo = 0;       // centers from this label on carry positions of the view
+    double guard = 0.0;         // no center is accepted at or below it
+};
+
+static void ek_view_scatter_back(ek_ctx *c, EkViewRun &v)
+{
+    ek_launch_view_scatter(c->v_act, v.n, c->v_dist, c->v_assign, c->dist, c->assign,
+                           c->hist, v.label_lo, c->hist_cap, c->ctl, c->goff, c->stream);
+    v.on = false;
+}
+
+static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
+                            int32_t max_new, double dist_cutoff, int32_t *n_added,
+                            int64_t *center_index_out, float *center_dist_out,
+                            float *final_maxdist, EkViewRun &view);
+
 static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
                          int32_t max_new, double dist_cutoff, int32_t *n_added,
                          int64_t *center_index_out, float *center_dist_out,
                          float *final_maxdist)
+{
+    EkViewRun view;
+    const int rc = ek_run_rounds_in(c, Tmax, first_label, max_new, dist_cutoff, n_added,
+                                    center_index_out, center_dist_out, final_maxdist, view);
+    if (rc != EK_OK && view.on) {
+        // an error under a view: distances, labels and history back in the shard's
+        // own space all the same (what is pending stays unapplied, as without a view)
+        ek_view_scatter_back(c, view);
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipGetLastError();
+    }
+    return rc;
+}
+
+static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
+                            int32_t max_new, double dist_cutoff, int32_t *n_added,
+                            int64_t *center_index_out, float *center_dist_out,
+                            float *final_maxdist, EkViewRun &view)
 {
     int rc = ek_spec_alloc(c);
     if (rc)
@@ -1126,7 +1251,7 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
     EK_HIP(ek_wait(c));
     for (int m = 0; m < EK_N_FORMS; ++m)
         c->st_rounds[m] = c->st_centers[m] = 0;
-    const int nb = (int)((c->n + EK_BLOCK - 1) / EK_BLOCK);
+    c->view_stats[0] = c->view_stats[1] = c->view_stats[2] = c->view_stats[3] = 0;
     // Triangle inequality (option key 11; reference `use_triangle_inequality`,
     // kcenters.py:287-296): one center at a time, tiles that cannot change are
     // not read.  Needs every frame's distance to be the one to the center its
@@ -1204,18 +1329,10 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
     int32_t gap = 8;            // centers until another form is tried again
     int32_t since = 0;          // centers since one last was
     EkRound R;
-    R.dist = c->dist;
-    R.assign = c->assign;
     R.vecs = c->vecs;
-    R.n = c->n;
-    R.n_pad = c->n_pad;
     R.goff = c->goff;
     R.A = c->A;
     R.T = Tmax;
-    R.tiles = c->tiles;
-    R.qtiles = c->qtiles;
-    R.aos = c->aos;
-    R.G = c->G;
     R.recs = c->recsT;
     R.plan = c->plan;
     R.pend = c->pend;
@@ -1226,8 +1343,7 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
     // (the per-prefix maxima in the pass: where they pay -- shards of up to ~half a
     // million frames: 10 % of a fit at 125 000; at 10^6 the pass's extra instructions
     // cost what the chain kernel's sweep did, profiles/r06/sweep_ab_*.log)
-    R.sweep = (fused && (c->pass_sweep == 2 ||
-                         (c->pass_sweep == 1 && c->n <= (int64_t)2048 * EK_TILE))) ? 1 : 0;
+    // (R.sweep: with the store, below)
     R.top = c->top;
     R.ctile = c->ctile;
     R.ctrace = c->ctrace;
@@ -1236,9 +1352,49 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
     R.tick = c->tick;
     R.rows = c->rows;
     R.vmask = c->vmask;
-    R.cutoff = dist_cutoff;
     R.ti_tab = tri ? c->ti_rtab : nullptr;
     R.ti_stats = tri ? c->ti_stats : nullptr;
+    // ---- the store the rounds see (S): the shard's own, or its active view ----------
+    EkStore S;
+    int nb = 0;
+    auto use_store = [&](bool the_view) {
+        if (the_view)
+            S = EkStore{c->v_dist, c->v_assign, c->v_tiles, c->v_qtiles, c->v_aos, c->v_G,
+                        view.n, (view.n + EK_TILE - 1) / EK_TILE * EK_TILE};
+        else
+            S = EkStore{c->dist, c->assign, c->tiles, c->qtiles, c->aos, c->G, c->n,
+                        c->n_pad};
+        nb = (int)((S.n + EK_BLOCK - 1) / EK_BLOCK);
+        R.dist = S.dist;
+        R.assign = S.assign;
+        R.n = S.n;
+        R.n_pad = S.n_pad;
+        R.tiles = S.tiles;
+        R.qtiles = S.qtiles;
+        R.aos = S.aos;
+        R.G = S.G;
+        R.sweep = (fused && (c->pass_sweep == 2 ||
+                             (c->pass_sweep == 1 && S.n <= (int64_t)2048 * EK_TILE))) ? 1 : 0;
+        // (under a view no center is accepted at or below its guard: the stop rule
+        // itself refuses it -- chain walk, plan and step kernel alike)
+        R.cutoff = the_view ? std::max(dist_cutoff, view.guard) : dist_cutoff;
+    };
+    use_store(false);
+    // Active view (option key 24): needs distances that ARE the distance to the center
+    // the label names, a metric, the fused rounds, and the triangle option off (its
+    // kernels read hist[].gidx as positions of old centers)
+    int view_mode = (c->state_exact && c->A >= 3 && fused && !c->tri && !c->view_nomem)
+                        ? c->active_view : 0;
+    bool view_skip = true;      // no look at the policy before a batch gave a maximum
+    // the whole store again: what is pending applied, the view's results scattered
+    auto leave_view = [&](bool &pending_) {
+        if (pending_) {
+            ek_launch_round_flush(R, c->stream);
+            pending_ = false;
+        }
+        ek_view_scatter_back(c, view);
+        use_store(false);
+    };
     bool pending = false;       // a fused round may have left a chain to apply
     int ti_pause = 0, ti_pause_next = 2;            // batches without masks / the next pause
     bool masks_fresh = false;   // ti_tmask describes the plan the next pass will run
@@ -1272,6 +1428,83 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
         const bool masks = tri && fused && form >= 4 && ti_pause == 0;
         R.tmask = masks ? c->ti_tmask : nullptr;
         R.pick_cap = cap;
+        // ---- active view: enter, rebuild or stay, by the maximum the last batch left --
+        if (view_mode && view_skip) {
+            view_skip = false;
+        } else if (view_mode && std::isfinite(cr.last_max)) {
+            // frames at up to theta are settled while centers are accepted above
+            // guard = 2 theta (1 + rel) + abs = rho x the maximum now
+            const double th = (EK_VIEW_RHO * (double)cr.last_max - EK_VIEW_ABS) /
+                              (2.0 * (1.0 + EK_VIEW_REL));
+            float theta = (float)th;
+            if ((double)theta > th)
+                theta = std::nextafterf(theta, 0.f);
+            const bool forced = view_mode == 2;
+            const int64_t want_cap =
+                forced ? c->n : (int64_t)std::ceil(EK_VIEW_SHRINK * (double)c->n);
+            if (theta > 0.f && ek_view_alloc(c, want_cap) == EK_OK) {
+                // how many frames a view built now would hold: those of this store
+                // above theta (what is pending not applied: a few too many) and, under
+                // a view, the shard's frames outside it that a lower theta lets in
+                // again (the shard's own copy of the view's frames is as old as the
+                // view: every one of them counts there)
+                uint32_t cnt[2] = {0, 0};
+                ek_launch_view_select(S.dist, S.n, theta, c->v_blockcnt, nullptr, nullptr, 0,
+                                      c->v_count, c->stream);
+                if (view.on)
+                    ek_launch_view_select(c->dist, c->n, theta, c->v_blockcnt, nullptr,
+                                          nullptr, 0, c->v_count + 1, c->stream);
+                EK_CHECK_LAUNCH();
+                EK_HIP(hipMemcpyAsync(cnt, c->v_count, sizeof(cnt), hipMemcpyDeviceToHost,
+                                      c->stream));
+                EK_HIP(ek_wait(c));
+                const int64_t est = (int64_t)cnt[0] +
+                                    (view.on ? std::max<int64_t>(0, (int64_t)cnt[1] - view.n)
+                                             : 0);
+                const bool build =
+                    forced ? est < c->n
+                           : ((double)est <= EK_VIEW_SHRINK * (double)S.n &&
+                              (double)left >= EK_VIEW_MIN_ROUNDS * std::max(per_round, 1.0));
+                if (build) {
+                    if (view.on) {
+                        leave_view(pending);
+                    } else if (pending) {
+                        ek_launch_round_flush(R, c->stream);
+                        pending = false;
+                    }
+                    uint32_t nv = 0;
+                    ek_launch_view_select(c->dist, c->n, theta, c->v_blockcnt,
+                                          c->v_blockoff, c->v_act, c->view_cap, c->v_count,
+                                          c->stream);
+                    EK_CHECK_LAUNCH();
+                    EK_HIP(hipMemcpyAsync(&nv, c->v_count, sizeof(nv),
+                                          hipMemcpyDeviceToHost, c->stream));
+                    EK_HIP(ek_wait(c));
+                    if (nv > 0 && (int64_t)nv < c->n && (int64_t)nv <= c->view_cap) {
+                        view.n = nv;
+                        view.label_lo = cr.n_done;
+                        view.guard = 2.0 * (double)theta * (1.0 + EK_VIEW_REL) + EK_VIEW_ABS;
+                        ek_launch_view_gather(c->v_act, view.n, c->A, c->aos, c->G, c->dist,
+                                              c->assign, c->v_aos, c->v_tiles, c->v_G,
+                                              c->v_dist, c->v_assign, c->stream);
+                        if (c->qt_valid)
+                            ek_launch_quad_tiles(c->v_tiles, (view.n + EK_TILE - 1) / EK_TILE,
+                                                 c->A, c->v_qtiles, c->stream);
+                        EK_CHECK_LAUNCH();
+                        view.on = true;
+                        use_store(true);
+                        EK_HIP(hipMemsetAsync(c->vmask, 0,
+                                              (size_t)(S.n_pad / EK_WAVE) * sizeof(uint32_t),
+                                              c->stream));
+                        c->view_stats[0]++;
+                    }
+                    held = -1;  // the pick in the new space, from a recomputed blockmax
+                }
+            } else if (theta > 0.f) {
+                (void)hipGetLastError();
+                view_mode = 0;  // (no memory for it: the run is what it was without)
+            }
+        }
         // ---- the record(s) this form starts from -------------------------------------
         if (held != form) {
             if (pending) {      // leaving a fused form: the state as it stands
@@ -1279,10 +1512,10 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
                 pending = false;
             } else if (held <= 1) {
                 // the step kernel's partials are per FPL frames
-                ek_launch_blockmax(c->dist, c->n, c->blockmax, c->stream);
+                ek_launch_blockmax(S.dist, S.n, c->blockmax, c->stream);
             }
             if (one) {
-                ek_launch_pick(c->blockmax, nb, c->dist, c->tiles, c->G, c->n,
+                ek_launch_pick(c->blockmax, nb, S.dist, S.tiles, S.G, S.n,
                                c->A, c->goff, c->recsT, c->ctl, c->stream);
             } else if (fused) {
                 ek_launch_round_chain(R, 1, c->stream);
@@ -1290,7 +1523,7 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
                 ek_launch_round_ti(R, goal, c->stream);
                 masks_fresh = R.tmask != nullptr;
             } else {
-                ek_launch_pickT(c->blockmax, nb, c->tiles, c->G, c->assign, c->A,
+                ek_launch_pickT(c->blockmax, nb, S.tiles, S.G, S.assign, c->A,
                                 form, c->goff, c->recsT, c->ctl, c->top,
                                 c->stream);
             }
@@ -1311,6 +1544,12 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
         else
             batch = std::max(2, std::min(256, (int32_t)(std::min(left, due) /
                                                         per_round) + 1));
+        // (the policy of the active view looks at the state between batches; forced
+        // views -- tests -- are rebuilt every other round)
+        if (view_mode == 2)
+            batch = std::min(batch, 2);
+        else if (view_mode && !one)
+            batch = std::min(batch, EK_VIEW_BATCH);
         EK_HIP(hipEventRecord(c->evb0, c->stream));
         if (R.tmask && !masks_fresh) {  // (after a pause: the masks of the plan at hand)
             ek_launch_round_ti(R, goal, c->stream);
@@ -1323,22 +1562,24 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
                 const int label = cr.n_done + r;
                 const bool skip = tri && label >= 1;
                 if (skip)
-                    ek_launch_ti(c->aos, c->G, c->A, c->hist, label, c->goff,
-                                 c->recsT, c->ti_D, c->dist, c->assign, c->n,
+                    ek_launch_ti(S.aos, S.G, c->A, c->hist, label, c->goff,
+                                 c->recsT, c->ti_D, S.dist, S.assign, S.n,
                                  c->ctl, c->ti_skip, c->ti_stats, c->stream);
-                ek_launch_step(fpl, 0, nt, c->tiles, c->G, c->dist, c->assign,
-                               c->scratch, c->recsT, 1, c->n, c->A, label,
-                               dist_cutoff, c->blockmax, c->hist, c->ctl, c->stream,
+                ek_launch_step(fpl, 0, nt, S.tiles, S.G, S.dist, S.assign,
+                               c->scratch, c->recsT, 1, S.n, c->A, label,
+                               R.cutoff, c->blockmax, c->hist, c->ctl, c->stream,
                                skip ? c->ti_skip : nullptr);
-                ek_launch_pick(c->blockmax, ek_step_blocks(fpl, c->n), c->dist,
-                               c->tiles, c->G, c->n, c->A, c->goff, c->recsT,
+                ek_launch_pick(c->blockmax, ek_step_blocks(fpl, S.n), S.dist,
+                               S.tiles, S.G, S.n, c->A, c->goff, c->recsT,
                                c->ctl, c->stream);
                 EK_CHECK_LAUNCH();
                 continue;
             }
             // sampled timing of the dominant kernel (bench.py)
+            // (only passes over the whole store: bench.py's roofline multiplies the
+            // sampled time by the shard's frames per launch)
             const bool sample =
-                c->samp_every > 0 && (c->samp_count++ % c->samp_every) == 0 &&
+                !view.on && c->samp_every > 0 && (c->samp_count++ % c->samp_every) == 0 &&
                 2 * (size_t)c->samp_used + 1 < c->samp_ev.size();
             if (sample)
                 c->samp_form[c->samp_used] = form;
@@ -1359,12 +1600,12 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
                 pending = true;
                 continue;
             }
-            ek_launch_plan(c->recsT, form, c->A, form, dist_cutoff, c->planD,
+            ek_launch_plan(c->recsT, form, c->A, form, R.cutoff, c->planD,
                            c->plan, c->hist, c->ctl, c->stream);
             if (sample)
                 EK_HIP(hipEventRecord(c->samp_ev[2 * c->samp_used], c->stream));
-            ek_launch_pass(form, c->tiles, c->qtiles, c->G, c->dist, c->assign,
-                           c->vecs, c->n, c->n_pad, c->A, c->recsT, c->plan,
+            ek_launch_pass(form, S.tiles, S.qtiles, S.G, S.dist, S.assign,
+                           c->vecs, S.n, S.n_pad, c->A, c->recsT, c->plan,
                            c->blockmax, c->ctile, c->ctrace, c->stream);
             if (sample) {
                 EK_HIP(hipEventRecord(c->samp_ev[2 * c->samp_used + 1],
@@ -1372,23 +1613,23 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
                 c->samp_used++;
             }
             if (c->chain) {
-                ek_launch_chain_max(c->dist, c->vecs, c->n, c->n_pad, c->plan,
+                ek_launch_chain_max(S.dist, c->vecs, S.n, S.n_pad, c->plan,
                                     c->pm, 1, c->goff, c->stream);
                 ek_launch_chain_decide_local(c->blockmax, c->pm, nb,
-                                             ek_chain_max_blocks(c->n), c->goff,
-                                             dist_cutoff, c->plan, c->hist,
+                                             ek_chain_max_blocks(S.n), c->goff,
+                                             R.cutoff, c->plan, c->hist,
                                              c->ctl, c->stream);
-                ek_launch_chain_apply(c->vecs, c->n, c->n_pad, c->dist, c->assign,
+                ek_launch_chain_apply(c->vecs, S.n, S.n_pad, S.dist, S.assign,
                                       c->plan, c->blockmax, c->stream);
             } else {
                 for (int j = 1; j < form; ++j) {
-                    ek_launch_localmax_check(c->blockmax, nb, c->goff, dist_cutoff,
+                    ek_launch_localmax_check(c->blockmax, nb, c->goff, R.cutoff,
                                              c->plan, c->hist, c->ctl, c->stream);
-                    ek_launch_apply(c->vecs, c->G, c->n, c->n_pad, c->A, c->dist,
-                                    c->assign, c->plan, c->blockmax, c->stream);
+                    ek_launch_apply(c->vecs, S.G, S.n, S.n_pad, c->A, S.dist,
+                                    S.assign, c->plan, c->blockmax, c->stream);
                 }
             }
-            ek_launch_pickT(c->blockmax, nb, c->tiles, c->G, c->assign, c->A, form,
+            ek_launch_pickT(c->blockmax, nb, S.tiles, S.G, S.assign, c->A, form,
                             c->goff, c->recsT, c->ctl, c->top, c->stream);
             EK_CHECK_LAUNCH();
         }
@@ -1421,6 +1662,28 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
         rounds_before = cr.n_rounds;
         c->st_rounds[ek_form_slot(form)] += ran;
         c->st_centers[ek_form_slot(form)] += got;
+        c->view_stats[1] += (int64_t)ran * S.n;
+        c->view_stats[2] += (int64_t)ran * (c->n - S.n);
+        if (view.on && cr.stopped) {
+            // The view's maximum is at or below its guard (or the cut-off): the
+            // centers from here on may move settled frames, and the shard's maximum
+            // may be one of them.  Back to the whole store, which decides whether
+            // this is the run's stop; the next look at the policy comes after a batch
+            // has given the shard's own maximum.
+            if ((double)cr.last_max > dist_cutoff)
+                c->view_stats[3]++;
+            leave_view(pending);
+            const int32_t zero = 0;     // (what the stop latched: the flag; the plan's
+            // `go` is made again by the bootstrap, the limit never changed)
+            EK_HIP(hipMemcpyAsync(&c->ctl->stopped, &zero, sizeof(zero),
+                                  hipMemcpyHostToDevice, c->stream));
+            EK_HIP(ek_wait(c));
+            cr.stopped = 0;
+            held = -1;
+            view_skip = true;
+            if (cr.n_done < goal)
+                continue;
+        }
         if (cr.stopped || cr.n_done >= goal)
             break;
         if (!one)
@@ -1503,7 +1766,28 @@ static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
     }
     if (pending) {              // the last round's accepted chain
         ek_launch_round_flush(R, c->stream);
+        pending = false;
         EK_CHECK_LAUNCH();
+    }
+    if (view.on || (held < 0 && cr.n_done > first_label)) {
+        // The run ends under a view (or just left one): results back, then the
+        // records and the maximum of the state as the whole store has it -- what the
+        // last round's pick leaves without a view.
+        if (view.on)
+            leave_view(pending);
+        ek_launch_blockmax(S.dist, S.n, c->blockmax, c->stream);
+        if (form == 1) {
+            ek_launch_pick(c->blockmax, nb, S.dist, S.tiles, S.G, S.n, c->A, c->goff,
+                           c->recsT, c->ctl, c->stream);
+        } else {
+            R.T = form;
+            ek_launch_round_chain(R, 1, c->stream);
+            ek_launch_round_next(R, 1, c->stream);
+        }
+        EK_CHECK_LAUNCH();
+        held = form;
+        EK_HIP(hipMemcpyAsync(&cr, c->ctl, sizeof(cr), hipMemcpyDeviceToHost, c->stream));
+        EK_HIP(ek_wait(c));
     }
     if (tri) {
         unsigned long long st[2] = {0, 0};
@@ -1618,6 +1902,15 @@ extern "C" int ek_kcenters_run(ek_ctx *c, int32_t first_label, int32_t max_new,
         if (rc)
             return rc;
     }
+    return EK_OK;
+}
+
+extern "C" int ek_view_stats(ek_ctx *c, int64_t *stats)
+{
+    if (!c || !stats)
+        return ek_fail(EK_EARG, "ek_view_stats: NULL argument");
+    for (int k = 0; k < 4; ++k)
+        stats[k] = c->view_stats[k];
     return EK_OK;
 }
 

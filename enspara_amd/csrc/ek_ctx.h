@@ -285,6 +285,21 @@ struct ek_ctx {
     int64_t st_centers[EK_N_FORMS] = {0, 0, 0, 0, 0};   // centers they accepted
     hipEvent_t evb0 = nullptr, evb1 = nullptr;   // per-batch timing
 
+    // active view (ek_view.hip, ek_run_rounds): a second frame store of the frames no
+    // round can leave out, sized once for view_cap frames (whole tiles) and kept
+    int active_view = 1;             // 0 never, 1 by the policy, 2 forced (EK_OPT_ACTIVE_VIEW)
+    bool view_nomem = false;         // there was no memory for it: runs as without
+    int64_t view_cap = 0;
+    float *v_aos = nullptr, *v_tiles = nullptr, *v_qtiles = nullptr;
+    double *v_G = nullptr;
+    float *v_dist = nullptr;
+    int32_t *v_assign = nullptr;
+    uint32_t *v_act = nullptr;       // [view_cap] positions in the shard, ascending
+    uint32_t *v_blockcnt = nullptr, *v_blockoff = nullptr;   // select scratch
+    uint32_t *v_count = nullptr;     // [2]
+    // of the last run: views built, frames x rounds streamed, left out, guard exits
+    int64_t view_stats[4] = {0, 0, 0, 0};
+
     // rounds across shards (ek_mshard.hip)
     EkMsState *ms = nullptr;         // device-side state
     unsigned char *ms_mbox = nullptr;    // own mailbox area [2][world][msg]
@@ -363,4 +378,5 @@ int ek_ensure_hist(ek_ctx *c, int32_t label);
 void ek_pam_forget(ek_ctx *c);
 int ek_upload_centers(ek_ctx *c, const float *xyz, int32_t K);
 int ek_free_all(ek_ctx *c);
+void ek_view_free(ek_ctx *c);     // the active view's buffers (ek_run_rounds)
 

@@ -1,0 +1,33 @@
+// ek_view.h -- the active view of a shard (ek_view.hip): the frames a k-centers round
+// can still change, compacted in ascending order into a second, smaller frame store.
+// Host side declarations only; the distance kernels know nothing of it.
+#pragma once
+#include "ek_common.h"
+
+#define EK_VIEW_SEL 1024    // frames per workgroup of the select kernels
+
+// scratch of a selection: per-workgroup counts and their exclusive scan
+static inline size_t ek_view_sel_blocks(int64_t n)
+{
+    return (size_t)((n + EK_VIEW_SEL - 1) / EK_VIEW_SEL);
+}
+// count[0] = frames of dist[0 .. n) with dist > theta (NaN counts: it is not settled);
+// with act != nullptr also act[p] = their positions, ascending, for p < act_cap.
+// blockcnt / blockoff: ek_view_sel_blocks(n) entries each (blockoff only with act).
+void ek_launch_view_select(const float *dist, int64_t n, float theta, uint32_t *blockcnt,
+                           uint32_t *blockoff, uint32_t *act, int64_t act_cap,
+                           uint32_t *count, hipStream_t s);
+// the view's store from the shard's: bit copies of the centred frames (frame-major and
+// frame-minor tiles), traces, distances and labels of frames act[0 .. n_v); the slots of
+// padding of the last tile are zeros
+void ek_launch_view_gather(const uint32_t *act, int64_t n_v, int A, const float *aos,
+                           const double *G, const float *dist, const int32_t *assign,
+                           float *aos_v, float *tiles_v, double *G_v, float *dist_v,
+                           int32_t *assign_v, hipStream_t s);
+// dist[act[p]] = dist_v[p], assign[act[p]] = assign_v[p]; the centers accepted under
+// the view (labels label_lo .. n_done - 1, n_done read from ctl) get their positions in
+// the shard: hist[l].gidx = goff + act[hist[l].gidx - goff]
+void ek_launch_view_scatter(const uint32_t *act, int64_t n_v, const float *dist_v,
+                            const int32_t *assign_v, float *dist, int32_t *assign,
+                            EkHist *hist, int32_t label_lo, int32_t label_cap,
+                            const EkCtl *ctl, int64_t goff, hipStream_t s);

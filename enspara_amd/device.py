@@ -565,6 +565,16 @@ class FrameStore:
         _lib.check(self.lib.ek_ti_stats(self._h, C.byref(t), C.byref(k)))
         return t.value, k.value
 
+    def view_stats(self):
+        """Active view (set_option("active_view", ...)) of the last kcenters_run:
+        -> {"views": built, "streamed": frames x rounds streamed, "left_out":
+        frames x rounds not streamed, "guard_exits": views the falling maximum
+        ended}"""
+        s = np.zeros(4, dtype=np.int64)
+        _lib.check(self.lib.ek_view_stats(self._h, _lib.i64p(s)))
+        return {"views": int(s[0]), "streamed": int(s[1]), "left_out": int(s[2]),
+                "guard_exits": int(s[3])}
+
     def history(self, first, count):
         idx = np.empty(max(count, 1), dtype=np.int64)
         cd = np.empty(max(count, 1), dtype=np.float32)

@@ -282,6 +282,10 @@ int ek_run_stats(ek_ctx *ctx, int64_t *passes, int64_t *centers);
  * how many of them it did not have to read because no frame of the tile could
  * come closer to the new center than it is to its own. */
 int ek_ti_stats(ek_ctx *ctx, int64_t *tiles, int64_t *skipped);
+/* Active view (EK_OPT_ACTIVE_VIEW) of the last ek_kcenters_run: stats[0] views built,
+ * [1] frames x rounds streamed, [2] frames x rounds left out, [3] views ended by
+ * their guard (the maximum fell to it before the run stopped). */
+int ek_view_stats(ek_ctx *ctx, int64_t *stats);
 
 /* history written by ek_kcenters_step: for labels [first, first+count) the
  * global frame index and pre-update distance of each accepted center;
@@ -882,7 +886,19 @@ enum ek_option {
      * again in an exchange of its own (0: rounds 3-5; what ek_ms_local / ek_ms_global,
      * whose exchange is the caller's collective, always do).  Every rank of a group must
      * hold the same value.  MEASUREMENT */
-    EK_OPT_MS_TWO_PHASE = 23
+    EK_OPT_MS_TWO_PHASE = 23,
+    /* ek_kcenters_run, single shard, fused rounds: stream only the frames a round can
+     * still change.  A frame at distance d <= theta from its center cannot be changed
+     * by a center accepted at 2 theta or more (triangle inequality, with the margin
+     * of EK_OPT_TRIANGLE), so between two batches of rounds the frames above theta
+     * are compacted -- ascending, bit copies -- into a second frame store, the rounds
+     * run on it with a stop rule that refuses every center at or below the guard
+     * 2 theta, and their results are scattered back.  Centers, labels and distances
+     * are unchanged.  0 never, 1 (default) when the view would stream at most 0.8 x
+     * the frames streamed now, 2 forced: rebuilt every other round whenever a frame is
+     * settled (tests).  Off with EK_OPT_TRIANGLE, an uploaded state, fewer than 3
+     * atoms, or no memory for the second store. */
+    EK_OPT_ACTIVE_VIEW = 24
 };
 int ek_set_option(ek_ctx *ctx, int32_t key, int32_t value);
 /* the value an option holds (what ek_set_option stored, or its default) */

@@ -46,6 +46,8 @@ SYMBOLS = [
     "ek_pam_propose_center",
     "ek_msm_counts", "ek_msm_counts_ctx", "ek_msm_row_normalize",
     "ek_msm_mle_prinz", "ek_msm_bace_prune", "ek_msm_bace_run",
+    "ek_lu_solve", "ek_lu_set_timing", "ek_lu_last_timing",
+    "ek_tpt_committors", "ek_tpt_mfpts_sinks", "ek_tpt_mfpts_all", "ek_tpt_fluxes",
     "ek_krylov_create", "ek_krylov_destroy", "ek_krylov_set_vector",
     "ek_krylov_get_vector", "ek_krylov_step", "ek_krylov_rotate",
     "ek_krylov_combine", "ek_krylov_expand", "ek_krylov_set_filter",
@@ -218,6 +220,14 @@ def load():
     L.ek_msm_bace_prune.argtypes = [C.c_int, i32, f64p, f64p, f32p]
     L.ek_msm_bace_run.argtypes = [C.c_int, i32, f64p, f64p, i32p, i32, i32, i32, vp,
                                   i32, f32p]
+    L.ek_lu_solve.argtypes = [C.c_int, i32, f64p, i32, f64p, f64p, i32p, i32p]
+    L.ek_lu_set_timing.argtypes = [C.c_int]
+    L.ek_lu_last_timing.argtypes = [f64p, f64p]
+    L.ek_tpt_committors.argtypes = [C.c_int, i32, f64p, i32p, i32, i32p, i32, f64p, i32p]
+    L.ek_tpt_mfpts_sinks.argtypes = [C.c_int, i32, f64p, i32p, i32, C.c_double, f64p, i32p]
+    L.ek_tpt_mfpts_all.argtypes = [C.c_int, i32, f64p, f64p, C.c_double, f64p, i32p]
+    L.ek_tpt_fluxes.argtypes = [C.c_int, i32, f64p, i32p, i32, i32p, i32, f64p, i32, f64p,
+                                f64p, i32p]
     L.ek_krylov_create.argtypes = [C.c_int, i64, i64p, i32p, f64p, i32,
                                    C.POINTER(vp)]
     L.ek_krylov_destroy.argtypes = [vp]

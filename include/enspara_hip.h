@@ -558,6 +558,55 @@ int ek_msm_bace_run(int device, int32_t n, const double *c, const double *w,
                     int32_t n_merges, void *records_out, int32_t dmat_steps,
                     float *dmat_out);
 
+/* ---- dense float64 solve and transition path theory ------------------------------
+ * ek_lu_solve: X = A^-1 B by a blocked LU with partial pivoting (the largest |a|
+ * of a column, the lowest row on ties), the trailing update on the matrix cores.
+ * All arrays are host memory, row-major: A [n][n], B and X [n][nrhs], 1 <= nrhs <=
+ * n <= 32768.  pivots_out (may be null) [n]: the row exchanged with row k at step
+ * k.  *info_out = -1, or the first column (from 0) whose pivot was zero or NaN: A
+ * is singular to working precision and X is not a solution.  EK_ENOMEM (and no
+ * allocation) if the device has not the memory for the padded [A | B].
+ * ek_lu_set_timing(1) makes the calls below record, per kind of launch, the time
+ * between HIP events; ek_lu_last_timing gives the last call's sums: ms_out[7] =
+ * assembly and epilogue, panel, exchange, block-row solve, trailing update, back
+ * substitution diagonal blocks, back substitution updates; gemm_flops_out[2] = the
+ * flops of the trailing updates and of the back substitution's.  Tools only: one
+ * call at a time. */
+int ek_lu_solve(int device, int32_t n, const double *A, int32_t nrhs, const double *B,
+                double *X, int32_t *pivots_out, int32_t *info_out);
+int ek_lu_set_timing(int on);
+int ek_lu_last_timing(double *ms_out, double *gemm_flops_out);
+/* Transition path theory (enspara/tpt/core.py, enspara/tpt/tpt.py).  T is dense,
+ * row-major [n][n], host memory, n at most 32768; sources / sinks are state
+ * indices below n, at least one each, no state in both (EK_EARG otherwise).  T is
+ * uploaded once, the system assembled, solved (as ek_lu_solve) and the result
+ * finished on the device; *info_out as ek_lu_solve's.  EK_ENOMEM if the device
+ * has not the memory (all-to-all: about 3 n^2 doubles).
+ * ek_tpt_committors replaces committors (core.py:40-102): sources and sinks made
+ * absorbing (_I_m_Q, :25-37), (I - Q) q = r with r = the sum over the sinks, in
+ * the order given, of T[:, s], r[sinks] = 1, r[sources] = 0 -- one solve where
+ * the reference takes one per sink and sums; q_out[n], q[sinks] = 1 and
+ * q[sources] = 0 exactly.
+ * ek_tpt_mfpts_sinks replaces mfpts with sinks (:143-154): t_out[n] = lagtime *
+ * (I - Q)^-1 c, c = 1 off the sinks, 0 on them.
+ * ek_tpt_mfpts_all replaces mfpts without (:133-139): Z = ((I - T) + W)^-1, every
+ * row of W = pops[n]; mfpt_out[n][n] = (lagtime * (Z_jj - Z_ij)) / pops[j].
+ * ek_tpt_fluxes replaces reactive_fluxes and net_fluxes (tpt.py:48-125): the
+ * committors as above into q_out[n], then flux_out[n][n] = (T_ij * (pops[i] *
+ * (1 - q_i))) * q_j with a zero diagonal, or with net != 0 max(f_ij - f_ji, 0). */
+int ek_tpt_committors(int device, int32_t n, const double *T, const int32_t *sources,
+                      int32_t n_sources, const int32_t *sinks, int32_t n_sinks,
+                      double *q_out, int32_t *info_out);
+int ek_tpt_mfpts_sinks(int device, int32_t n, const double *T, const int32_t *sinks,
+                       int32_t n_sinks, double lagtime, double *t_out,
+                       int32_t *info_out);
+int ek_tpt_mfpts_all(int device, int32_t n, const double *T, const double *pops,
+                     double lagtime, double *mfpt_out, int32_t *info_out);
+int ek_tpt_fluxes(int device, int32_t n, const double *T, const int32_t *sources,
+                  int32_t n_sources, const int32_t *sinks, int32_t n_sinks,
+                  const double *pops, int32_t net, double *q_out, double *flux_out,
+                  int32_t *info_out);
+
 /* ---- leading eigenpairs of a sparse transition matrix ---------------------------
  * Device primitives of an Arnoldi / Krylov-Schur solver replacing the ARPACK /
  * LAPACK calls of eigenspectrum (enspara/msm/transition_matrices.py:173-233).

@@ -48,6 +48,8 @@ SYMBOLS = [
     "ek_msm_mle_prinz", "ek_msm_bace_prune", "ek_msm_bace_run",
     "ek_lu_solve", "ek_lu_set_timing", "ek_lu_last_timing",
     "ek_tpt_committors", "ek_tpt_mfpts_sinks", "ek_tpt_mfpts_all", "ek_tpt_fluxes",
+    "ek_mi_open", "ek_mi_add", "ek_mi_load_counts", "ek_mi_counts", "ek_mi_information",
+    "ek_mi_last_timing", "ek_mi_close",
     "ek_krylov_create", "ek_krylov_destroy", "ek_krylov_set_vector",
     "ek_krylov_get_vector", "ek_krylov_step", "ek_krylov_rotate",
     "ek_krylov_combine", "ek_krylov_expand", "ek_krylov_set_filter",
@@ -228,6 +230,14 @@ def load():
     L.ek_tpt_mfpts_all.argtypes = [C.c_int, i32, f64p, f64p, C.c_double, f64p, i32p]
     L.ek_tpt_fluxes.argtypes = [C.c_int, i32, f64p, i32p, i32, i32p, i32, f64p, i32, f64p,
                                 f64p, i32p]
+    u8p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    L.ek_mi_open.argtypes = [C.c_int, i32, i32, i32, i32, C.POINTER(vp)]
+    L.ek_mi_add.argtypes = [vp, u8p, u8p, i64]
+    L.ek_mi_load_counts.argtypes = [vp, u32p, C.c_uint64]
+    L.ek_mi_counts.argtypes = [vp, u32p]
+    L.ek_mi_information.argtypes = [vp, f64p]
+    L.ek_mi_last_timing.argtypes = [vp, f64p]
+    L.ek_mi_close.argtypes = [vp]
     L.ek_krylov_create.argtypes = [C.c_int, i64, i64p, i32p, f64p, i32,
                                    C.POINTER(vp)]
     L.ek_krylov_destroy.argtypes = [vp]

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 OUT = os.path.join(HERE, "libenspara_hip.so")
 SOURCES = ["ek_prepare.hip", "ek_kcenters.hip", "ek_spec.hip", "ek_pass16.hip", "ek_chain.hip", "ek_round.hip", "ek_view.hip", "ek_mshard.hip", "ek_assign.hip", "ek_pam.hip", "ek_pam_sparse.hip",
-           "ek_msm.hip", "ek_msm_mle.hip", "ek_msm_bace.hip", "ek_lu.hip", "ek_tpt.hip", "ek_krylov.hip", "ek_features.hip", "ek_feat_assign.hip", "ek_api.hip", "ek_api_pam.hip",
+           "ek_msm.hip", "ek_msm_mle.hip", "ek_msm_bace.hip", "ek_lu.hip", "ek_tpt.hip", "ek_mi.hip", "ek_krylov.hip", "ek_features.hip", "ek_feat_assign.hip", "ek_api.hip", "ek_api_pam.hip",
            "ek_api_ms.hip"]
 HEADERS = ["ek_common.h", "ek_ctx.h", "ek_qcp.h", "ek_reduce.h", "ek_chain_dev.h", "ek_top_dev.h", "ek_pam_sparse.h", "ek_lanes.h", "ek_pw.h", "ek_feat.h", "ek_view.h", "ek_lu.h",
            os.path.join("..", "..", "include",

@@ -607,6 +607,38 @@ int ek_tpt_fluxes(int device, int32_t n, const double *T, const int32_t *sources
                   const double *pops, int32_t net, double *q_out, double *flux_out,
                   int32_t *info_out);
 
+/* ---- joint counts and mutual information of discrete features ----------------------
+ * Replaces libinfo.matrix_bincount2d / bincount2d (enspara/info_theory/libinfo.pyx)
+ * and the arithmetic of mutual_information (mutual_info.py:290-327).  A handle owns
+ * the counts jc [fx][fy][nx][ny] uint32 on the device, zero when opened; 1 <= nx,
+ * ny <= 255 (code 255 pads the frame axis and is no state), fx, fy <= 65535 * 64
+ * (EK_EARG naming the limit).  All arrays are host memory.
+ * ek_mi_add counts one trajectory into them: X [frames][fx], Y [frames][fy] state
+ * codes as bytes, row-major, Y null = X against itself (fx == fy, nx == ny); 0 <=
+ * frames < 2^31 - 64, and the frames of all calls stay below 2^32 (EK_EARG).  A code
+ * that is no state of its feature (>= nx resp. ny) counts nowhere; the caller
+ * validates.  The product of the two one-hot matrices runs on the int8 matrix cores
+ * and its partial sums are added with integer atomics: the counts do not depend on
+ * how the frames are split.  EK_ENOMEM if the device has not the memory for the
+ * codes twice over.
+ * ek_mi_load_counts replaces the counts by uploaded ones; n_obs is the largest sum
+ * over a feature pair's cells, below 2^32 (the caller's to compute), and what later
+ * ek_mi_add calls count on from.  ek_mi_counts downloads them.
+ * ek_mi_information: mi_out [fx][fy] float64, per pair the sum over u (outer) and v
+ * (inner) of P_uv * log(P_uv / (P_u * P_v)) with P = count / n_obs and the marginals
+ * exact integer sums; terms with a zero P are skipped, nothing is fused; a pair
+ * without observations gives 0.
+ * ek_mi_last_timing: ms_out[3] = the last ek_mi_add's upload and pack, its count
+ * kernel, the last ek_mi_information's kernel, between HIP events. */
+typedef struct ek_mi ek_mi;
+int ek_mi_open(int device, int32_t fx, int32_t fy, int32_t nx, int32_t ny, ek_mi **out);
+int ek_mi_add(ek_mi *h, const uint8_t *X, const uint8_t *Y, int64_t frames);
+int ek_mi_load_counts(ek_mi *h, const uint32_t *jc, uint64_t n_obs);
+int ek_mi_counts(ek_mi *h, uint32_t *jc_out);
+int ek_mi_information(ek_mi *h, double *mi_out);
+int ek_mi_last_timing(ek_mi *h, double *ms_out);
+int ek_mi_close(ek_mi *h);
+
 /* ---- leading eigenpairs of a sparse transition matrix ---------------------------
  * Device primitives of an Arnoldi / Krylov-Schur solver replacing the ARPACK /
  * LAPACK calls of eigenspectrum (enspara/msm/transition_matrices.py:173-233).

@@ -28,7 +28,8 @@
 //           64 values in registers
 //   gemm    A22 -= L21 U12: 64 x 64 tiles of C per workgroup, four waves of 32 x 32,
 //           L21 (negated, which is exact) and U12 staged through the LDS in halves
-//           of 32, 16 MFMAs of 16x16x4 per 16 x 16 tile
+//           of 32, 16 MFMAs of 16x16x4 per 16 x 16 tile; the 64 products are summed
+//           from zero and added to C once
 // Back substitution, per panel from the last: the diagonal block (U in the LDS, one
 // thread per right-hand side), then the rows above through the same gemm kernel.
 //
@@ -415,15 +416,21 @@ lu_gemm_kernel(double *__restrict__ a, size_t ld, int32_t crow0, int32_t ccol0,
     const size_t rbase = (size_t)crow0 + (size_t)blockIdx.y * EK_LU_NB;
     const size_t cbase = (size_t)ccol0 + (size_t)blockIdx.x * EK_LU_NB;
 
-    ek_v4d acc[2][2];
+    // The products are summed from zero and added to C once.  Summed into C they were
+    // rounded at C's magnitude 16 times per launch, n / 4 times over a factorisation:
+    // eta_dev grew like sqrt(n) (11 eta_ref on a dominant matrix at n = 1100), where a
+    // BLAS, which sums this way, stays flat.
+    ek_v4d acc[2][2], cin[2][2];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[mi][ni][i] = a[(rbase + wm + mi * 16 + l4 + 4 * i) * ld + cbase + wn +
+            for (int i = 0; i < 4; ++i) {
+                cin[mi][ni][i] = a[(rbase + wm + mi * 16 + l4 + 4 * i) * ld + cbase + wn +
                                    ni * 16 + l15];
+                acc[mi][ni][i] = 0.0;
+            }
 
     for (int kh = 0; kh < 2; ++kh) {
         if (kh)
@@ -456,7 +463,7 @@ lu_gemm_kernel(double *__restrict__ a, size_t ld, int32_t crow0, int32_t ccol0,
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 a[(rbase + wm + mi * 16 + l4 + 4 * i) * ld + cbase + wn + ni * 16 + l15] =
-                    acc[mi][ni][i];
+                    cin[mi][ni][i] + acc[mi][ni][i];
 }
 
 static void lu_gemm(double *aug, size_t ld, int32_t crow0, int32_t nrows, int32_t ccol0,

@@ -29,6 +29,14 @@ __all__ = ["committors", "mfpts"]
 # the solver's panel width (EK_LU_NB of csrc/ek_lu.h): systems are padded to
 # whole panels on the device
 LU_PANEL = 64
+# where the solver's kernels change form (csrc/ek_lu.hip; nothing here computes
+# with them: the tests place their shapes around them).  A sub-panel's thread t
+# keeps rows c0 + t + LU_PANEL_WG * i, i < LU_SUB_RPT, in registers and leaves the
+# rows from c0 + LU_PANEL_WG * LU_SUB_RPT on in memory; the back substitution runs
+# a workgroup per LU_COL_WG right-hand sides.
+LU_PANEL_WG = 1024      # LU_PANEL_WG
+LU_SUB_RPT = 4          # LU_SUB_RPT
+LU_COL_WG = 256         # LU_COL_WG
 
 
 def _dense_tprob(tprob):

@@ -17,23 +17,28 @@ LD = np.longdouble
 
 
 # ---- the solver ---------------------------------------------------------------------
-def lu_solve(A, B):
+def lu_solve(A, B, return_gaps=False):
     """Gaussian elimination with partial pivoting (largest |a|, first row on
     ties) on [A | B], unblocked, then back substitution -> (X, pivots, info):
     pivots[k] = the row exchanged with row k, info = -1 or the first column with
-    a zero or NaN pivot (that column is left as it is and the run goes on)."""
+    a zero or NaN pivot (that column is left as it is and the run goes on).
+
+    return_gaps: -> (X, pivots, info, gaps) with gaps[k] = (m1 - m2) / m1, m1 >= m2
+    the two largest |a| among step k's candidates: how far the choice of the pivot
+    is from a tie (0 on a tie or a column of zeros; inf for a single candidate).
+    Another summation order may choose another row only where this is rounding."""
     A = np.array(A, dtype=np.float64)
     n = A.shape[0]
     B = np.array(B, dtype=np.float64)
     vector = B.ndim == 1
     M = np.concatenate([A, B.reshape(n, -1)], axis=1)
     piv = np.zeros(n, dtype=np.int32)
+    gaps = np.full(n, np.inf)
     info = -1
     for k in range(n):
-        col = np.abs(M[k:, k])
-        col = np.where(np.isnan(col), np.inf, col)
-        p = k + int(np.argmax(col))
-        piv[k] = p
+        p, gap = _pivot(M[k:, k], return_gaps)
+        p += k
+        piv[k], gaps[k] = p, gap
         if p != k:
             M[[k, p]] = M[[p, k]]
         pv = M[k, k]
@@ -50,7 +55,43 @@ def lu_solve(A, B):
             X[k] = X[k] / M[k, k]
             X[:k] -= M[:k, k][:, None] * X[k][None, :]
     X = np.ascontiguousarray(X)
-    return (X[:, 0] if vector else X), piv, info
+    X = X[:, 0] if vector else X
+    return (X, piv, info, gaps) if return_gaps else (X, piv, info)
+
+
+def _pivot(col, want_gap=True):
+    """(offset of the pivot in the candidates col, the relative gap to the runner-up)"""
+    col = np.abs(col)
+    col = np.where(np.isnan(col), np.inf, col)
+    gap = np.inf
+    if want_gap and len(col) > 1:
+        m2, m1 = np.partition(col, len(col) - 2)[-2:]
+        gap = (m1 - m2) / m1 if 0 < m1 < np.inf else 0.0
+    return int(np.argmax(col)), gap
+
+
+def leading_pivots(A, w):
+    """(pivots, info, gaps) of lu_solve's first w steps, from A's first w columns
+    alone (what is right of them changes no choice among them)"""
+    M = np.array(np.asarray(A)[:, :w], dtype=np.float64)
+    piv = np.zeros(w, dtype=np.int32)
+    gaps = np.full(w, np.inf)
+    info = -1
+    for k in range(w):
+        p, gaps[k] = _pivot(M[k:, k])
+        p += k
+        piv[k] = p
+        if p != k:
+            M[[k, p]] = M[[p, k]]
+        pv = M[k, k]
+        if pv == 0 or pv != pv:
+            if info < 0:
+                info = k
+            continue
+        l = M[k + 1:, k] / pv
+        M[k + 1:, k] = l
+        M[k + 1:, k + 1:] -= l[:, None] * M[k, k + 1:][None, :]
+    return piv, info, gaps
 
 
 def solve(A, B):
@@ -155,6 +196,71 @@ def chain_counts(n, seed, cross=0.01, steps=None):
     return C + C.T + np.eye(n, dtype=np.int64)
 
 
+def weighted_chain(n, seed=0):
+    """(T, pops) of a reversible metastable chain without the sampled walk (too
+    slow in Python above a few hundred states): symmetric weights, heavy inside
+    10 blocks, light across"""
+    rng = np.random.RandomState(seed)
+    block = np.arange(n) * 10 // n
+    W = rng.rand(n, n) * np.where(block[:, None] == block[None, :], 1.0, 1e-3)
+    W = W + W.T + np.diag(0.3 * n * rng.rand(n))
+    return W / W.sum(axis=1)[:, None], W.sum(axis=1) / W.sum()
+
+
+# the sizes of tests/test_gpu_lu_large.py: the first keeps rows in a thread's second
+# register slot, the second in all four slots and in memory behind them
+LU_N_SLOTS, LU_N_TAIL = 1100, 4200
+
+
+def _distinct(groups, n):
+    idx = np.array(groups, dtype=np.int64).reshape(-1)
+    assert len(set(idx.tolist())) == idx.size and idx.min() >= 0 and idx.max() < n, \
+        "indices are distinct and in [0, %d)" % n
+    assert all(list(g) == sorted(g) for g in groups), "every group ascends"
+
+
+def swapped_dominant(n, pairs, seed=0):
+    """(A, pivots): D = rand(n, n) + n I with rows k and r exchanged for every
+    (k, r) of pairs, k < r, the pairs disjoint.  The diagonal dominates every
+    column throughout the elimination (entries right of it change by about 1 / n
+    per step), so step k finds D's row k, which lies in row r: pivots[k] = r
+    and pivots[j] = j for every other j, r included"""
+    _distinct(pairs, n)
+    A = np.random.RandomState(seed).rand(n, n) + n * np.eye(n)
+    piv = np.arange(n, dtype=np.int32)
+    for k, r in pairs:
+        A[[k, r]] = A[[r, k]]
+        piv[k] = r
+    return A, piv
+
+
+def tie_system(n, triples):
+    """(A, pivots) for triples (k, r1, r2, s), k < r1 < r2, s = +1 or -1, all
+    indices distinct.  From the identity: A[k, k] = 0, A[k, r1] = 1, A[r1, r1] = 0,
+    A[r1, k] = s, A[r2, k] = -s.  Column k then holds exactly two candidates, s in
+    row r1 and -s in row r2, equal in |a|: the rule (largest |a|, lowest row) gives
+    pivots[k] = r1, and pivots[j] = j everywhere else (after the exchange row r1
+    is e_r1, and row r2 only gains the multiplier 1 in column k).  The elimination
+    is exact in integers, and so is the solution for an integer B: x[r1] = b[k],
+    x[k] = s b[r1], x[r2] = b[r2] + b[r1]"""
+    _distinct([t[:3] for t in triples], n)
+    A = np.eye(n)
+    piv = np.arange(n, dtype=np.int32)
+    for k, r1, r2, s in triples:
+        assert s in (1, -1)
+        A[k, k] = 0.0
+        A[k, r1] = 1.0
+        A[r1, r1] = 0.0
+        A[r1, k] = s
+        A[r2, k] = -s
+        piv[k] = r1
+    return A, piv
+
+
+def small_integer_rhs(n, nrhs=2):
+    return np.arange(nrhs * n, dtype=np.float64).reshape(n, nrhs) % 7 - 3
+
+
 def tprob_from_counts(C):
     C = np.asarray(C, dtype=np.float64)
     return C / C.sum(axis=1)[:, None]
@@ -178,6 +284,18 @@ def backward_error(A, X, B):
     def ninf(M):
         return float(np.abs(M).sum(axis=1).max())
     return ninf(R) / (ninf(A) * ninf(X2) + ninf(B2))
+
+
+def check_backward(tag, A, B, X):
+    """the backward criterion: eta(X) <= 8 max(eta_ref, u), eta_ref that of
+    numpy.linalg.solve on the same system; prints both and returns the ratio"""
+    eta = backward_error(A, X, B)
+    eta_ref = backward_error(A, np.linalg.solve(A, B), B)
+    ratio = eta / max(eta_ref, U)
+    print("%-22s eta_dev %.2f u  eta_ref %.2f u  eta_dev / max(eta_ref, u) = %.2f (<= 8)"
+          % (tag, eta / U, eta_ref / U, ratio))
+    assert eta <= 8 * max(eta_ref, U)
+    return ratio
 
 
 def forward_bound(err_ref, x_hp):

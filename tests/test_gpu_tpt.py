@@ -10,7 +10,11 @@ criteria, both relative to the reference's own error:
             x_hp and the real reference's error err_ref of tests/golden/tpt_golden.npz
 Shapes: the reference's 3- and 4-state tables; n = 17 (one MFMA tile and a bit); 63,
 64, 65 around the panel width; 130 (two panels and a ragged third, once with
-cross = 1e-5: ill-conditioned); 300.  Every test prints the ratios it measures."""
+cross = 1e-5: ill-conditioned); 300.  tests/test_gpu_lu_large.py goes on where the
+kernels of the LU change form, at the constants LU_PANEL_WG = 1024, LU_SUB_RPT = 4 and
+LU_COL_WG = 256 (enspara_amd/tpt/core.py): n = 1100 (rows in a thread's second register
+slot), 4200 (all four slots and rows left in memory), and 257 / 300 right-hand sides at
+n = 300 (two workgroups of them).  Every test prints the ratios it measures."""
 import os
 
 import numpy as np
@@ -20,7 +24,7 @@ import scipy.sparse
 import _numpy_tpt as nt
 from enspara_amd import tpt
 from enspara_amd.exception import DataInvalid
-from enspara_amd.tpt.core import LU_PANEL, _solve
+from enspara_amd.tpt.core import LU_COL_WG, LU_PANEL, LU_PANEL_WG, LU_SUB_RPT, _solve
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +51,20 @@ TIES5 = np.array([[0, -4, 4, -4, -2], [1, 3, -4, 2, 4], [-1, 0, 1, -3, -4],
 def test_panel_width_is_the_one_the_shapes_assume():
     assert LU_PANEL == 64 and [G["C_" + c].shape[0] for c in CHAINS] == [
         17, LU_PANEL - 1, LU_PANEL, LU_PANEL + 1, 130, 130, 300]
+
+
+def test_large_sizes_straddle_the_constants_of_the_kernels():
+    """tests/test_gpu_lu_large.py: if this fails the kernels were retuned, and the
+    sizes (and the tables of rows there) move with the constants named here"""
+    def pad(n):
+        return -(-n // LU_PANEL) * LU_PANEL
+    n1, n4, tail = nt.LU_N_SLOTS, nt.LU_N_TAIL, LU_PANEL_WG * LU_SUB_RPT
+    # rows in slot 1 and in no other; n still affordable for nt.lu_solve
+    assert LU_PANEL_WG + LU_PANEL < n1 and pad(n1) <= 2 * LU_PANEL_WG and n1 <= 1200
+    # real rows in the tail for more than a panel of columns, one per thread at most
+    assert tail + LU_PANEL < n4 and pad(n4) <= tail + LU_PANEL_WG
+    # the golden n300: a second, ragged block of right-hand sides
+    assert LU_COL_WG < 257 < 300 and pad(300) <= 2 * LU_COL_WG
 
 
 def _chain(chain):
@@ -168,12 +186,7 @@ def test_reactive_populations(chain):
 
 
 # ---- the solver: backward error ------------------------------------------------------------------
-def _check_backward(tag, A, B, X):
-    eta = nt.backward_error(A, X, B)
-    eta_ref = nt.backward_error(A, np.linalg.solve(A, B), B)
-    print("%-22s eta_dev %.2f u  eta_ref %.2f u  eta_dev / max(eta_ref, u) = %.2f (<= 8)"
-          % (tag, eta / nt.U, eta_ref / nt.U, eta / max(eta_ref, nt.U)))
-    assert eta <= 8 * max(eta_ref, nt.U)
+_check_backward = nt.check_backward
 
 
 @pytest.mark.parametrize("chain", CHAINS)
@@ -191,6 +204,8 @@ def test_backward_error_on_the_golden_systems(chain):
     for what in ("t1", "t3"):
         A, c = nt.mfpt_sink_system(T, G["snk_%s_%s" % (chain, what)])
         _check_backward("%s_%s" % (chain, what), A, c, _device(chain, what))
+    # (the long-double residual of n right-hand sides; n300's all-to-all system, with its
+    # two workgroups of right-hand sides, is tests/test_gpu_lu_large.py's)
     if n <= 130:
         A, eye = nt.mfpt_all_system(T, pops)
         Z = _solve(A, eye)

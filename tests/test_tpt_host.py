@@ -181,3 +181,96 @@ def test_lu_restatement_pivots_and_singularity():
     assert steps <= 3
     R = nt.exact_residual(M, X, M @ xt)
     assert np.abs(R).max() < 1e-17
+
+
+# ---- what tests/test_gpu_lu_large.py leans on ----------------------------------------------
+def test_lu_constants_are_those_of_the_kernels():
+    import re
+    from enspara_amd.tpt import core
+    src = open(os.path.join(os.path.dirname(os.path.abspath(core.__file__)), os.pardir, "csrc",
+                            "ek_lu.hip")).read()
+    for name in ("LU_PANEL_WG", "LU_SUB_RPT", "LU_COL_WG"):
+        defs = re.findall(r"^#define %s (\d+)\b" % name, src, flags=re.M)
+        assert defs == [str(getattr(core, name))], name
+    assert (core.LU_PANEL_WG, core.LU_SUB_RPT, core.LU_COL_WG) == (1024, 4, 256)
+    assert (nt.LU_N_SLOTS, nt.LU_N_TAIL) == (1100, 4200)
+
+
+def test_exchanged_pairs_give_the_predicted_pivots():
+    """the constructor of the large GPU test at n = 200, pairs scaled to fit (both
+    edges, neighbours, a k late in the matrix)"""
+    n = 200
+    pairs = [(0, 64), (1, 199), (2, 127), (3, 128), (8, 100), (9, 110), (63, 65), (70, 198),
+             (120, 121), (150, 197)]
+    A, want = nt.swapped_dominant(n, pairs, seed=n)
+    assert [int(want[k]) for k, _ in pairs] == [r for _, r in pairs]
+    assert int(np.sum(want != np.arange(n))) == len(pairs)
+    B = np.random.RandomState(1).rand(n, 3)
+    X, piv, info, gaps = nt.lu_solve(A, B, return_gaps=True)
+    assert info == -1 and np.array_equal(piv, want)
+    # (nowhere near a tie: the diagonal's n against entries of about 1)
+    assert gaps[:-1].min() > 0.9 and gaps[-1] == np.inf
+    assert nt.backward_error(A, X, B) <= 4 * nt.U
+    with pytest.raises(AssertionError):
+        nt.swapped_dominant(n, [(0, 64), (64, 70)])
+    with pytest.raises(AssertionError):
+        nt.swapped_dominant(n, [(5, 3)])
+
+
+def test_tie_system_gives_the_predicted_pivots_and_an_integer_solution():
+    n = 200
+    triples = [(0, 100, 129, 1), (10, 28, 152, -1), (3, 50, 196, -1), (26, 175, 195, 1),
+               (70, 111, 161, -1), (130, 198, 199, 1)]
+    A, want = nt.tie_system(n, triples)
+    assert set(np.unique(A)) == {-1.0, 0.0, 1.0}
+    for k, r1, r2, s in triples:
+        assert list(np.flatnonzero(A[:, k])) == [r1, r2] and A[r1, k] == -A[r2, k] == s
+        assert want[k] == r1
+    B = nt.small_integer_rhs(n)
+    X, piv, info, gaps = nt.lu_solve(A, B, return_gaps=True)
+    assert info == -1 and np.array_equal(piv, want)
+    assert sorted(np.flatnonzero(gaps == 0)) == sorted(t[0] for t in triples)
+    assert np.array_equal(X, np.round(X)) and np.array_equal(A @ X, B)
+    for k, r1, r2, s in triples:
+        assert np.array_equal(X[r1], B[k]) and np.array_equal(X[k], s * B[r1])
+        assert np.array_equal(X[r2], B[r2] + B[r1])
+    with pytest.raises(AssertionError):
+        nt.tie_system(n, [(0, 5, 9, 1), (1, 9, 12, 1)])
+
+
+def test_lu_gaps_against_a_direct_computation():
+    # every intermediate a small dyadic rational: the elimination below is exact
+    A = np.array([[2, 1, 0, 1, 0, 3], [-4, 1, 2, 0, 1, 0], [4, 3, 1, 1, 0, 2],
+                  [1, 0, -2, 4, 1, 1], [0, 2, 1, 0, -3, 1], [2, 0, 1, 1, 1, 4]], dtype=np.float64)
+    X, piv, info, gaps = nt.lu_solve(A, np.eye(6), return_gaps=True)
+    M = A.copy()
+    want_piv, want_gaps = [], []
+    for k in range(6):
+        cand = sorted(((abs(M[r, k]), -r) for r in range(k, 6)), reverse=True)
+        p = -cand[0][1]
+        want_piv.append(p)
+        want_gaps.append((cand[0][0] - cand[1][0]) / cand[0][0] if k < 5 else np.inf)
+        M[[k, p]] = M[[p, k]]
+        for r in range(k + 1, 6):
+            M[r, k:] -= (M[r, k] / M[k, k]) * M[k, k:]
+    assert info == -1 and list(piv) == want_piv
+    assert want_gaps[0] == 0.0 and want_piv[0] == 1     # -4 and 4 tie: the first row
+    assert np.array_equal(gaps, want_gaps)
+    assert np.array_equal(nt.lu_solve(A, np.eye(6))[0], X)
+    # the first columns alone give the first pivots
+    piv3, info3, gaps3 = nt.leading_pivots(A, 3)
+    assert info3 == -1 and list(piv3) == want_piv[:3] and np.array_equal(gaps3, want_gaps[:3])
+    # a column of zeros below the diagonal: gap 0, and the zero pivot reported
+    S = np.array([[2., 1., 1.], [2., 1., 1.], [0., 1., 3.]])
+    _, _, infoS, gapsS = nt.lu_solve(S, np.ones(3), return_gaps=True)
+    assert infoS == 2 and gapsS[0] == 0.0
+
+
+def test_weighted_chain_is_a_reversible_chain():
+    T, pops = nt.weighted_chain(120, seed=3)
+    assert np.abs(T.sum(axis=1) - 1).max() < 1e-14 and abs(pops.sum() - 1) < 1e-14
+    assert np.abs(pops @ T - pops).max() < 1e-15
+    F = pops[:, None] * T
+    assert np.abs(F - F.T).max() < 1e-15
+    block = np.arange(120) * 10 // 120
+    assert T[block[:, None] != block[None, :]].max() < 1e-3

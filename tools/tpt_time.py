@@ -30,14 +30,7 @@ from enspara_amd import _lib, tpt  # noqa: E402
 KINDS = ["other", "panel", "swap", "trsm", "gemm", "back_trsm", "back_gemm"]
 
 
-def chain(n, seed=0):
-    """a reversible metastable chain without the sampled walk (too slow in Python at
-    these sizes): symmetric weights, heavy inside 10 blocks, light across"""
-    rng = np.random.RandomState(seed)
-    block = np.arange(n) * 10 // n
-    W = rng.rand(n, n) * np.where(block[:, None] == block[None, :], 1.0, 1e-3)
-    W = W + W.T + np.diag(0.3 * n * rng.rand(n))
-    return W / W.sum(axis=1)[:, None], W.sum(axis=1) / W.sum()
+chain = nt.weighted_chain     # the chain tests/test_gpu_lu_large.py checks results on
 
 
 def timed(fn, repeat=2):

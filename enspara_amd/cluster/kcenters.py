@@ -200,7 +200,7 @@ def _kcenters_host(traj, distance_method, n_clusters, dist_cutoff,
     """The reference's loop for an arbitrary callable metric
     (kcenters.py:195-311)."""
     # 'euclidean' / 'manhattan' (/ hamming) on a plain 2-D array: the loop runs
-    # on the device with the state resident there (csrc/ek_features.hip
+    # on the device with the state resident there (csrc/ek_feat_kcenters.hip
     # ek_feat_kcenters: same arithmetic per distance, same strict-< update, same
     # first-index arg-max) instead of one device metric call plus numpy passes
     # per center.  The triangle-inequality variant keeps the host loop.

@@ -24,7 +24,6 @@
 // (minimum, label) per sample, and a second launch scans the parts in ascending
 // order with the same strict < -- the first minimum of the first part that holds
 // it, which is the first minimum overall.
-#include "ek_common.h"
 #include "ek_feat.h"
 
 #include <algorithm>
@@ -43,7 +42,7 @@ feat_assign_kernel(const T *__restrict__ tiles, const T *__restrict__ C, int64_t
     __shared__ T cs[FA_FC][FA_TC];
     const int64_t f = (int64_t)blockIdx.x * EK_BLOCK + threadIdx.x;
     // (lanes past n read the zeros the last tile is padded with)
-    const T *p = tiles + (size_t)(f / EK_TILE) * (size_t)F * EK_TILE + (f % EK_TILE);
+    const T *p = feat_tile_ptr(tiles, f, F);
     const int k0 = (int)blockIdx.y * kper;
     const int k1 = (K - k0 < kper) ? K : k0 + kper;
     double best = __builtin_inf();
@@ -118,12 +117,11 @@ extern "C" int ek_feat_assign_nearest(ek_feat *k, int32_t metric, const void *ce
         return ek_set_error(EK_EARG, "ek_feat_assign_nearest: bad argument");
     if (!k->loaded)
         return ek_set_error(EK_ESTATE, "ek_feat_assign_nearest: no samples loaded");
-    if ((metric == 2) != (k->kind == 2))
-        return ek_set_error(EK_EARG, "ek_feat_assign_nearest: hamming needs integer "
-                                     "samples, the other metrics floating point");
-    FE_HIP(hipSetDevice(k->device));
-    int rc = feat_shard_alloc(k, 0);
+    int rc = feat_metric_ok(k, metric, "ek_feat_assign_nearest");
     if (rc)
+        return rc;
+    FE_HIP(hipSetDevice(k->device));
+    if ((rc = feat_shard_alloc(k, 0)))
         return rc;
     if (k->n == 0)
         return EK_OK;
@@ -159,25 +157,13 @@ extern "C" int ek_feat_assign_nearest(ek_feat *k, int32_t metric, const void *ce
         FE_HIP(hipMalloc((void **)&k->apart_c, cap * sizeof(int32_t)));
         k->apart_cap = cap;
     }
-#define FA_GO(T, M)                                                            \
-    hipLaunchKernelGGL((feat_assign_kernel<T, M>), dim3((unsigned)nb, parts),  \
-                       dim3(EK_BLOCK), 0, k->s, (const T *)k->tiles,           \
-                       (const T *)k->acent, k->n, k->F, K, kper, k->kdist,     \
-                       k->kassign, k->apart_d, k->apart_c)
-    if (metric == 2)
-        FA_GO(long long, 2);
-    else if (k->kind == 0) {
-        if (metric == 0)
-            FA_GO(float, 0);
-        else
-            FA_GO(float, 1);
-    } else {
-        if (metric == 0)
-            FA_GO(double, 0);
-        else
-            FA_GO(double, 1);
-    }
-#undef FA_GO
+    feat_dispatch(k, metric, [&](auto t, auto m) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((feat_assign_kernel<T, decltype(m)::value>),
+                           dim3((unsigned)nb, parts), dim3(EK_BLOCK), 0, k->s,
+                           (const T *)k->tiles, (const T *)k->acent, k->n, k->F, K, kper,
+                           k->kdist, k->kassign, k->apart_d, k->apart_c);
+    });
     FE_HIP(hipGetLastError());
     if (parts > 1) {
         hipLaunchKernelGGL(feat_assign_merge_kernel, dim3((unsigned)nb), dim3(EK_BLOCK), 0,

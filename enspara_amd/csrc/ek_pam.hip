@@ -1550,7 +1550,7 @@ void ek_launch_pw_tree(const float *dist, const int32_t *assign, int64_t n,
 }
 
 // chunk sums of both columns of `part` ([2 g + 0 / 1] leaf sums) and the totals,
-// chunks added left to right -> out2[0], out2[1]  (ek_features.hip: PAM over
+// chunks added left to right -> out2[0], out2[1]  (ek_feat_pam.hip: PAM over
 // float64 distances brings its own leaf kernel)
 __global__ void __launch_bounds__(EK_WAVE)
 ek_pw_total_kernel(const double *__restrict__ chunksum, int n_chunks,

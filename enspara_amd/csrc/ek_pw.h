@@ -1,4 +1,4 @@
-// ek_pw.h -- numpy's pairwise sum, the parts shared with ek_features.hip (ek_pam.hip)
+// ek_pw.h -- numpy's pairwise sum, the parts shared with ek_feat_pam.hip (ek_pam.hip)
 #pragma once
 #include "ek_common.h"
 

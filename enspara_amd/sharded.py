@@ -24,7 +24,7 @@ Feature metrics ('euclidean', 'manhattan', libdist.hamming on a 2-D array of
 samples) shard the same way: :class:`FeatureShard` speaks the one-record part
 of the protocol over an ``ek_feat`` handle -- record = (float64 local max
 distance, global index, that sample's features), one launch per center and
-rank (csrc/ek_features.hip ``feat_shard_step_kernel``) -- and
+rank (csrc/ek_feat_kcenters.hip ``feat_shard_step_kernel``) -- and
 :func:`fit_features_sharded` is the estimators' ``mpi_mode`` for them: same
 centers, labels and float64 distances as the single-process loop.  No rounds
 of several candidates, no mailbox transport and no sharded PAM there.

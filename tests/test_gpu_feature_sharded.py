@@ -1,5 +1,5 @@
 """k-centers with a feature metric over several shards on the device
-(csrc/ek_features.hip feat_shard_step_kernel; enspara_amd/sharded.py
+(csrc/ek_feat_kcenters.hip feat_shard_step_kernel; enspara_amd/sharded.py
 FeatureShard / fit_features_sharded).
 
 First group: the C ABI in one process -- 1, 2, 3 and 8 shards as separate

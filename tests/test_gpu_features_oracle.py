@@ -1,5 +1,6 @@
 """The feature-space kernels (csrc/ek_features.hip: libdist.euclidean /
-manhattan / hamming, the resident k-centers loop, the resident PAM sweep)
+manhattan / hamming; ek_feat_kcenters.hip: the resident k-centers loop;
+ek_feat_pam.hip: the resident PAM sweep)
 against the ORACLE (oracle/features.py, pinned to the reference's compiled
 module by test_features.py::test_oracle_matches_reference_libdist) -- never
 against another device form -- at the forms the library takes on real data:
@@ -7,7 +8,8 @@ feature counts across every staging chunk, partial tiles, every input dtype,
 the value edges of IEEE arithmetic, a matrix loaded in more than one chunk
 whose arg-max runs over thousands of block maxima and whose PAM sweep takes
 windows by size, more than 256 medoids (the tiled nearest search in several
-chunks), and windows of every width.  Exact throughout: float64 distances and
+chunks), windows of every width, and the resident loops one feature past
+the target's staging chunk.  Exact throughout: float64 distances and
 labels equal, the same centers and medoids, the same dtypes, the random stream
 left in the same place."""
 import numpy as np
@@ -354,3 +356,35 @@ def test_pam_windows_every_width(monkeypatch):
             got = _sweeps(X, name, inds, a, d, None, 4, 1, monkeypatch)
             moved += got[0] != inds
     assert moved >= 24
+
+
+# ---- (f) the resident loops across FY_CHUNK -------------------------------------------
+# feat_step_kernel (resident k-centers) and feat_dist_classify_kernel (the sweep's
+# plain path) stage the center / the proposal through feat_one_vs_all in pieces of
+# FY_CHUNK = 2048 features: one feature past it, a last tile of 300 - 256 samples.
+ACROSS = (("euclidean", np.float32), ("manhattan", np.float64), ("hamming", np.uint16))
+
+
+def _across_matrix(name, dt):
+    rng = np.random.RandomState(81)
+    if name == "hamming":
+        return rng.randint(0, 3, size=(300, 2049)).astype(dt)
+    return rng.normal(size=(300, 2049)).astype(dt)
+
+
+@pytest.mark.parametrize("name,dt", ACROSS)
+def test_resident_kcenters_across_fy_chunk(name, dt, resident_calls):
+    _check_kcenters(name, _across_matrix(name, dt), resident_calls, n_clusters=5)
+
+
+@pytest.mark.parametrize("name,dt", ACROSS)
+def test_pam_sweep_across_fy_chunk(name, dt, monkeypatch):
+    """5 medoids, drawn and explicit proposals: 2.4 MB or less of samples, so every
+    proposal takes its own pass over them (no window)."""
+    monkeypatch.delenv("EK_FEAT_PAM_WINDOWS", raising=False)
+    monkeypatch.delenv("EK_FEAT_PAM_SYNC", raising=False)
+    X = _across_matrix(name, dt)
+    assert X.nbytes < 64 << 20
+    inds, a, d = _start(X, name, 5)
+    _sweeps(X, name, inds, a, d, None, 4, 2, monkeypatch)
+    _sweeps(X, name, inds, a, d, [7, 299, 256, 100, 255], 4, 1, monkeypatch)

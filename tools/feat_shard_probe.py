@@ -1,5 +1,5 @@
 """Measurement only: microseconds per center of the sharded feature-space
-k-centers step (csrc/ek_features.hip feat_shard_step_kernel, ONE launch per
+k-centers step (csrc/ek_feat_kcenters.hip feat_shard_step_kernel, ONE launch per
 center and shard) against the resident single-handle loop ek_feat_kcenters
 (feat_step_kernel + feat_pick_kernel, two launches per center) on the same
 data, in the same process, alternating.

@@ -32,6 +32,7 @@ SYMBOLS = [
     "ek_spec_apply", "ek_spec_round_end", "ek_spec_progress", "ek_spec_rounds",
     "ek_spec_chain_bytes", "ek_spec_chain_rows", "ek_spec_chain_max",
     "ek_spec_chain_apply", "ek_run_stats", "ek_ti_stats", "ek_view_stats",
+    "ek_view_layout_check",
     "ek_ms_setup", "ek_ms_mailbox", "ek_ms_connect", "ek_ms_begin", "ek_ms_local",
     "ek_ms_global", "ek_ms_end", "ek_ms_run", "ek_ms_state", "ek_ms_diag",
     "ek_assign_nearest",
@@ -93,6 +94,8 @@ EK_OPT_PAM_PAIRS_MFMA = 21
 EK_OPT_PASS_SWEEP = 22
 EK_OPT_MS_TWO_PHASE = 23
 EK_OPT_ACTIVE_VIEW = 24
+EK_OPT_VIEW_RHO = 25
+EK_OPT_VIEW_RATIO = 26
 OPTIONS = {k[7:].lower(): v for k, v in list(globals().items())
            if k.startswith("EK_OPT_")}
 
@@ -179,6 +182,7 @@ def load():
     L.ek_ms_run.argtypes = [vp, i32, i32, C.c_double, i32p, i64p, f32p, f32p]
     L.ek_ti_stats.argtypes = [vp, i64p, i64p]
     L.ek_view_stats.argtypes = [vp, i64p]
+    L.ek_view_layout_check.argtypes = [vp, f32, i64p]
     L.ek_assign_nearest.argtypes = [vp, f32p, i32]
     f64p = C.POINTER(C.c_double)
     L.ek_ms_diag.argtypes = [vp, i64p, f64p]

@@ -642,10 +642,22 @@ extern "C" int ek_set_option(ek_ctx *c, int32_t key, int32_t value)
         c->pass_sweep = value;
         return EK_OK;
     case EK_OPT_ACTIVE_VIEW:
-        if (value < 0 || value > 2)
+        if (value < 0 || value > 3)
             return ek_fail(EK_EARG, "ek_set_option: active view 0 (never), 1 (by the "
-                                    "policy) or 2 (forced)");
+                                    "policy), 2 (forced) or 3 (forced, poisoned)");
         c->active_view = value;
+        return EK_OK;
+    case EK_OPT_VIEW_RHO:
+        if (value < 500 || value > 950)
+            return ek_fail(EK_EARG, "ek_set_option: active view's guard 500 .. 950 per "
+                                    "mille of the maximum");
+        c->view_rho = value;
+        return EK_OK;
+    case EK_OPT_VIEW_RATIO:
+        if (value < 500 || value > 950)
+            return ek_fail(EK_EARG, "ek_set_option: active view's rebuild ratio 500 .. "
+                                    "950 per mille of the frames streamed");
+        c->view_ratio = value;
         return EK_OK;
     case EK_OPT_ASSIGN_KERNEL:
         if (value < 0 || value > 3)
@@ -685,6 +697,8 @@ extern "C" int ek_get_option(ek_ctx *c, int32_t key, int32_t *value)
     case EK_OPT_PAM_ZERO_COPY: *value = c->pam_zero_copy; return EK_OK;
     case EK_OPT_PAM_PAIRS_MFMA: *value = ek_pam_pairs_form; return EK_OK;
     case EK_OPT_ACTIVE_VIEW: *value = c->active_view; return EK_OK;
+    case EK_OPT_VIEW_RHO: *value = c->view_rho; return EK_OK;
+    case EK_OPT_VIEW_RATIO: *value = c->view_ratio; return EK_OK;
     default:
         return ek_fail(EK_EARG, "ek_get_option: unknown key %d", key);
     }
@@ -1116,13 +1130,19 @@ extern "C" int ek_history_download(ek_ctx *c, int32_t first, int32_t count,
 // batch is timed on the device (centers per millisecond) and the other form is
 // tried for a short batch at intervals that double while it keeps losing.
 // ---- the active view (ek_view.hip; DESIGN.md 4a "Active view") ---------------------
-// The policy's two constants: a view's guard sits at EK_VIEW_RHO x the maximum it was
-// built at (frames at up to about half of that are settled), and a view is built when
-// it would stream at most EK_VIEW_SHRINK x the frames streamed now.
-static constexpr double EK_VIEW_RHO = 0.75;
-static constexpr double EK_VIEW_SHRINK = 0.8;
+// The policy's two numbers are options (EK_OPT_VIEW_RHO, EK_OPT_VIEW_RATIO, per mille):
+// a view's guard sits at rho x the maximum it was built at (frames at up to about half
+// of that are settled), and a view is built when it would stream at most ratio x the
+// frames streamed now.
 static constexpr int EK_VIEW_MIN_ROUNDS = 24;   // rounds left that make a rebuild worth it
 static constexpr int EK_VIEW_BATCH = 16;        // rounds between two looks at the policy
+// The look (ek_view_look_kernel) rides behind the last round of a batch and comes back
+// with the control word.  Looks that find nothing settled pause, as the triangle masks
+// do: 1, 2, 4, 8 batches after an estimate above EK_VIEW_IDLE x the frames streamed;
+// a paused batch may be EK_VIEW_PAUSED_BATCH rounds long.
+static constexpr double EK_VIEW_IDLE = 0.95;
+static constexpr int EK_VIEW_PAUSE_MAX = 8;
+static constexpr int EK_VIEW_PAUSED_BATCH = 4 * EK_VIEW_BATCH;
 static constexpr double EK_VIEW_REL = 1e-3, EK_VIEW_ABS = 1e-3;     // ek_round_ti_*'s margin
 
 void ek_view_free(ek_ctx *c)
@@ -1170,6 +1190,8 @@ static int ek_view_alloc(ek_ctx *c, int64_t frames)
     EK_VALLOC(c->v_blockcnt, nblk * sizeof(uint32_t));
     EK_VALLOC(c->v_blockoff, nblk * sizeof(uint32_t));
     EK_VALLOC(c->v_count, 2 * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->v_count, 0, 2 * sizeof(uint32_t), c->stream);
 #undef EK_VALLOC
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -1198,7 +1220,38 @@ struct EkViewRun {
     int64_t n = 0;              // frames in it
     int32_t label_lo = 0;       // centers from this label on carry positions of the view
     double guard = 0.0;         // no center is accepted at or below it
+    bool tiles_valid = false;   // v_tiles holds this view (built on demand from v_qtiles)
 };
+
+// 0xFF bytes all over the view's buffers (active view 3, ek_view_layout_check)
+static hipError_t ek_view_poison(ek_ctx *c)
+{
+    const size_t cap = (size_t)c->view_cap, nt = cap / EK_TILE, A3 = (size_t)3 * c->A;
+    hipError_t e = hipMemsetAsync(c->v_aos, 0xFF, cap * A3 * sizeof(float), c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->v_tiles, 0xFF, nt * A3 * EK_TILE * sizeof(float), c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->v_qtiles, 0xFF, ek_quad_tiles_bytes((int64_t)nt, c->A),
+                           c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->v_G, 0xFF, cap * sizeof(double), c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->v_dist, 0xFF, cap * sizeof(float), c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->v_assign, 0xFF, cap * sizeof(int32_t), c->stream);
+    return e;
+}
+
+// the view's store from the selection c->v_act[0 .. n_v): frame-major copy, traces,
+// distances, labels and the quad copy; without a quad copy in the context (rounds of 8
+// at most) the frame-minor tiles instead.  -> whether v_tiles holds the view
+static bool ek_view_build(ek_ctx *c, int64_t n_v)
+{
+    ek_launch_view_build(c->v_act, n_v, c->A, c->qt_valid, c->aos, c->G, c->dist, c->assign,
+                         c->v_aos, c->qt_valid ? c->v_qtiles : c->v_tiles, c->v_G, c->v_dist,
+                         c->v_assign, c->stream);
+    return !c->qt_valid;
+}
 
 static void ek_view_scatter_back(ek_ctx *c, EkViewRun &v)
 {
@@ -1385,7 +1438,11 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
     // kernels read hist[].gidx as positions of old centers)
     int view_mode = (c->state_exact && c->A >= 3 && fused && !c->tri && !c->view_nomem)
                         ? c->active_view : 0;
-    bool view_skip = true;      // no look at the policy before a batch gave a maximum
+    const bool forced = view_mode >= 2;
+    const double rho = c->view_rho / 1000.0, shrink = c->view_ratio / 1000.0;
+    bool looked = false;        // the last batch carried a look: look_cnt is its answer
+    uint32_t look_cnt[2] = {0, 0};
+    int look_pause = 0, look_pause_next = 1;        // batches without a look / the next pause
     // the whole store again: what is pending applied, the view's results scattered
     auto leave_view = [&](bool &pending_) {
         if (pending_) {
@@ -1428,43 +1485,38 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
         const bool masks = tri && fused && form >= 4 && ti_pause == 0;
         R.tmask = masks ? c->ti_tmask : nullptr;
         R.pick_cap = cap;
-        // ---- active view: enter, rebuild or stay, by the maximum the last batch left --
-        if (view_mode && view_skip) {
-            view_skip = false;
-        } else if (view_mode && std::isfinite(cr.last_max)) {
+        // ---- active view: enter, rebuild or stay, by the look the last batch carried ---
+        if (view_mode && looked && std::isfinite(cr.last_max)) {
+            looked = false;
             // frames at up to theta are settled while centers are accepted above
             // guard = 2 theta (1 + rel) + abs = rho x the maximum now
-            const double th = (EK_VIEW_RHO * (double)cr.last_max - EK_VIEW_ABS) /
+            const double th = (rho * (double)cr.last_max - EK_VIEW_ABS) /
                               (2.0 * (1.0 + EK_VIEW_REL));
             float theta = (float)th;
             if ((double)theta > th)
                 theta = std::nextafterf(theta, 0.f);
-            const bool forced = view_mode == 2;
-            const int64_t want_cap =
-                forced ? c->n : (int64_t)std::ceil(EK_VIEW_SHRINK * (double)c->n);
-            if (theta > 0.f && ek_view_alloc(c, want_cap) == EK_OK) {
-                // how many frames a view built now would hold: those of this store
+            if (theta > 0.f) {
+                // how many frames a view built now would hold (look_cnt, counted on the
+                // device at the theta of the same maximum): those of this store
                 // above theta (what is pending not applied: a few too many) and, under
                 // a view, the shard's frames outside it that a lower theta lets in
                 // again (the shard's own copy of the view's frames is as old as the
                 // view: every one of them counts there)
-                uint32_t cnt[2] = {0, 0};
-                ek_launch_view_select(S.dist, S.n, theta, c->v_blockcnt, nullptr, nullptr, 0,
-                                      c->v_count, c->stream);
-                if (view.on)
-                    ek_launch_view_select(c->dist, c->n, theta, c->v_blockcnt, nullptr,
-                                          nullptr, 0, c->v_count + 1, c->stream);
-                EK_CHECK_LAUNCH();
-                EK_HIP(hipMemcpyAsync(cnt, c->v_count, sizeof(cnt), hipMemcpyDeviceToHost,
-                                      c->stream));
-                EK_HIP(ek_wait(c));
-                const int64_t est = (int64_t)cnt[0] +
-                                    (view.on ? std::max<int64_t>(0, (int64_t)cnt[1] - view.n)
-                                             : 0);
+                const int64_t est =
+                    (int64_t)look_cnt[0] +
+                    (view.on ? std::max<int64_t>(0, (int64_t)look_cnt[1] - view.n) : 0);
                 const bool build =
                     forced ? est < c->n
-                           : ((double)est <= EK_VIEW_SHRINK * (double)S.n &&
+                           : ((double)est <= shrink * (double)S.n &&
                               (double)left >= EK_VIEW_MIN_ROUNDS * std::max(per_round, 1.0));
+                if (!forced) {
+                    if ((double)est > EK_VIEW_IDLE * (double)S.n) {
+                        look_pause = look_pause_next;
+                        look_pause_next = std::min(2 * look_pause_next, EK_VIEW_PAUSE_MAX);
+                    } else if (build || (double)est <= shrink * (double)S.n) {
+                        look_pause_next = 1;
+                    }
+                }
                 if (build) {
                     if (view.on) {
                         leave_view(pending);
@@ -1484,12 +1536,9 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
                         view.n = nv;
                         view.label_lo = cr.n_done;
                         view.guard = 2.0 * (double)theta * (1.0 + EK_VIEW_REL) + EK_VIEW_ABS;
-                        ek_launch_view_gather(c->v_act, view.n, c->A, c->aos, c->G, c->dist,
-                                              c->assign, c->v_aos, c->v_tiles, c->v_G,
-                                              c->v_dist, c->v_assign, c->stream);
-                        if (c->qt_valid)
-                            ek_launch_quad_tiles(c->v_tiles, (view.n + EK_TILE - 1) / EK_TILE,
-                                                 c->A, c->v_qtiles, c->stream);
+                        if (view_mode == 3)
+                            EK_HIP(ek_view_poison(c));
+                        view.tiles_valid = ek_view_build(c, view.n);
                         EK_CHECK_LAUNCH();
                         view.on = true;
                         use_store(true);
@@ -1500,10 +1549,15 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
                     }
                     held = -1;  // the pick in the new space, from a recomputed blockmax
                 }
-            } else if (theta > 0.f) {
-                (void)hipGetLastError();
-                view_mode = 0;  // (no memory for it: the run is what it was without)
             }
+        }
+        looked = false;
+        // (a view's frame-minor tiles are made when a kernel that reads them runs under
+        // it: the rounds of 8, the one-center step and its pick)
+        if (view.on && !view.tiles_valid && form < 16) {
+            ek_launch_view_tiles(c->v_qtiles, S.n_pad / EK_TILE, c->A, c->v_tiles, c->stream);
+            EK_CHECK_LAUNCH();
+            view.tiles_valid = true;
         }
         // ---- the record(s) this form starts from -------------------------------------
         if (held != form) {
@@ -1546,10 +1600,10 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
                                                         per_round) + 1));
         // (the policy of the active view looks at the state between batches; forced
         // views -- tests -- are rebuilt every other round)
-        if (view_mode == 2)
+        if (forced)
             batch = std::min(batch, 2);
         else if (view_mode && !one)
-            batch = std::min(batch, EK_VIEW_BATCH);
+            batch = std::min(batch, look_pause > 0 ? EK_VIEW_PAUSED_BATCH : EK_VIEW_BATCH);
         EK_HIP(hipEventRecord(c->evb0, c->stream));
         if (R.tmask && !masks_fresh) {  // (after a pause: the masks of the plan at hand)
             ek_launch_round_ti(R, goal, c->stream);
@@ -1634,6 +1688,28 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
             EK_CHECK_LAUNCH();
         }
         EK_HIP(hipEventRecord(c->evb1, c->stream));
+        // ---- the look for the next decision rides on this batch ----------------------
+        if (view_mode && look_pause > 0) {
+            --look_pause;
+        } else if (view_mode) {
+            const int64_t want_cap =
+                forced ? c->n : (int64_t)std::ceil(shrink * (double)c->n);
+            if (ek_view_alloc(c, want_cap) == EK_OK) {
+                EK_HIP(hipMemsetAsync(c->v_count, 0, sizeof(look_cnt), c->stream));
+                ek_launch_view_look(S.dist, S.n, c->ctl, rho, EK_VIEW_REL, EK_VIEW_ABS,
+                                    c->v_count, c->stream);
+                if (view.on)
+                    ek_launch_view_look(c->dist, c->n, c->ctl, rho, EK_VIEW_REL,
+                                        EK_VIEW_ABS, c->v_count + 1, c->stream);
+                EK_CHECK_LAUNCH();
+                EK_HIP(hipMemcpyAsync(look_cnt, c->v_count, sizeof(look_cnt),
+                                      hipMemcpyDeviceToHost, c->stream));
+                looked = true;
+            } else {
+                (void)hipGetLastError();
+                view_mode = 0;  // (no memory for it: the run is what it was without)
+            }
+        }
         const int32_t before = cr.n_done;
         EK_HIP(hipMemcpyAsync(&cr, c->ctl, sizeof(cr), hipMemcpyDeviceToHost,
                               c->stream));
@@ -1680,7 +1756,7 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
             EK_HIP(ek_wait(c));
             cr.stopped = 0;
             held = -1;
-            view_skip = true;
+            looked = false;     // (it counted in the view's space, against its maximum)
             if (cr.n_done < goal)
                 continue;
         }
@@ -1902,6 +1978,87 @@ extern "C" int ek_kcenters_run(ek_ctx *c, int32_t first_label, int32_t max_new,
         if (rc)
             return rc;
     }
+    return EK_OK;
+}
+
+extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
+{
+    if (!c || !out)
+        return ek_fail(EK_EARG, "ek_view_layout_check: NULL argument");
+    if (!c->loaded || c->n <= 0)
+        return ek_fail(EK_ESTATE, "ek_view_layout_check: no frames loaded");
+    EK_HIP(hipSetDevice(c->device));
+    out[0] = out[1] = out[2] = out[3] = 0;
+    int rc = ek_view_alloc(c, c->n);
+    if (rc)
+        return rc;
+    uint32_t nv = 0;
+    ek_launch_view_select(c->dist, c->n, theta, c->v_blockcnt, c->v_blockoff, c->v_act,
+                          c->view_cap, c->v_count, c->stream);
+    EK_CHECK_LAUNCH();
+    EK_HIP(hipMemcpyAsync(&nv, c->v_count, sizeof(nv), hipMemcpyDeviceToHost, c->stream));
+    EK_HIP(ek_wait(c));
+    out[0] = nv;
+    if (nv == 0 || (int64_t)nv > c->view_cap)
+        return EK_OK;
+    const size_t nt = ((size_t)nv + EK_TILE - 1) / EK_TILE, A3 = (size_t)3 * c->A;
+    const size_t tile_words = nt * A3 * EK_TILE;
+    const size_t quad_bytes = ek_quad_tiles_bytes((int64_t)nt, c->A);
+    // the earlier path into scratch: gather -> frame-minor tiles -> quad copy
+    float *r_aos = nullptr, *r_tiles = nullptr, *r_qtiles = nullptr, *r_dist = nullptr;
+    double *r_G = nullptr;
+    int32_t *r_assign = nullptr;
+    unsigned long long *diff = nullptr, got[3] = {0, 0, 0};
+    hipError_t e = hipMalloc((void **)&r_aos, (size_t)nv * A3 * sizeof(float));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&r_tiles, tile_words * sizeof(float));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&r_qtiles, quad_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&r_G, (size_t)nv * sizeof(double));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&r_dist, (size_t)nv * sizeof(float));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&r_assign, (size_t)nv * sizeof(int32_t));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&diff, sizeof(got));
+    if (e == hipSuccess)
+        e = hipMemsetAsync(diff, 0, sizeof(got), c->stream);
+    if (e == hipSuccess)
+        e = ek_view_poison(c);
+    if (e == hipSuccess) {
+        ek_launch_view_gather(c->v_act, nv, c->A, c->aos, c->G, c->dist, c->assign, r_aos,
+                              r_tiles, r_G, r_dist, r_assign, c->stream);
+        ek_launch_quad_tiles(r_tiles, (int64_t)nt, c->A, r_qtiles, c->stream);
+        // a rebuild, and the tiles a reader under the view would ask for
+        if (!ek_view_build(c, nv))
+            ek_launch_view_tiles(c->v_qtiles, (int64_t)nt, c->A, c->v_tiles, c->stream);
+        if (c->qt_valid)
+            ek_launch_view_diff(c->v_qtiles, r_qtiles, quad_bytes / 4, diff, c->stream);
+        ek_launch_view_diff(c->v_tiles, r_tiles, tile_words, diff + 1, c->stream);
+        ek_launch_view_diff(c->v_aos, r_aos, (size_t)nv * A3, diff + 2, c->stream);
+        ek_launch_view_diff(c->v_G, r_G, (size_t)nv * 2, diff + 2, c->stream);
+        ek_launch_view_diff(c->v_dist, r_dist, (size_t)nv, diff + 2, c->stream);
+        ek_launch_view_diff(c->v_assign, r_assign, (size_t)nv, diff + 2, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(got, diff, sizeof(got), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess)
+        e = ek_wait(c);
+    else
+        (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(r_aos);
+    (void)hipFree(r_tiles);
+    (void)hipFree(r_qtiles);
+    (void)hipFree(r_G);
+    (void)hipFree(r_dist);
+    (void)hipFree(r_assign);
+    (void)hipFree(diff);
+    EK_HIP(e);
+    out[1] = (int64_t)got[0];
+    out[2] = (int64_t)got[1];
+    out[3] = (int64_t)got[2];
     return EK_OK;
 }
 

@@ -287,7 +287,10 @@ struct ek_ctx {
 
     // active view (ek_view.hip, ek_run_rounds): a second frame store of the frames no
     // round can leave out, sized once for view_cap frames (whole tiles) and kept
-    int active_view = 1;             // 0 never, 1 by the policy, 2 forced (EK_OPT_ACTIVE_VIEW)
+    int active_view = 1;             // 0 never, 1 by the policy, 2 forced, 3 forced into
+                                     // poisoned buffers (EK_OPT_ACTIVE_VIEW)
+    int view_rho = 750;              // per mille: the guard over the maximum (EK_OPT_VIEW_RHO)
+    int view_ratio = 800;            // per mille: build at this share (EK_OPT_VIEW_RATIO)
     bool view_nomem = false;         // there was no memory for it: runs as without
     int64_t view_cap = 0;
     float *v_aos = nullptr, *v_tiles = nullptr, *v_qtiles = nullptr;

@@ -24,6 +24,23 @@ void ek_launch_view_gather(const uint32_t *act, int64_t n_v, int A, const float 
                            const double *G, const float *dist, const int32_t *assign,
                            float *aos_v, float *tiles_v, double *G_v, float *dist_v,
                            int32_t *assign_v, hipStream_t s);
+// the gather of a rebuild: as ek_launch_view_gather, but out_v is the view's QUAD copy
+// (quad: the layout of ek_launch_quad_tiles, whole tiles, zeros for the atoms past the
+// last and the frames of padding) or its frame-minor tiles (!quad)
+void ek_launch_view_build(const uint32_t *act, int64_t n_v, int A, bool quad, const float *aos,
+                          const double *G, const float *dist, const int32_t *assign,
+                          float *aos_v, float *out_v, double *G_v, float *dist_v,
+                          int32_t *assign_v, hipStream_t s);
+// frame-minor tiles from a quad copy (the inverse of ek_launch_quad_tiles), bit copies
+void ek_launch_view_tiles(const float *qtiles, int64_t n_tiles, int A, float *tiles,
+                          hipStream_t s);
+// count[0] += frames of dist[0 .. n) above theta, where theta is what the host derives
+// from ctl->last_max: (rho last_max - abs) / (2 (1 + rel)) in double, rounded down
+void ek_launch_view_look(const float *dist, int64_t n, const EkCtl *ctl, double rho, double rel,
+                         double abs_, uint32_t *count, hipStream_t s);
+// count[0] += 32-bit words of a[0 .. words) and b[0 .. words) that differ
+void ek_launch_view_diff(const void *a, const void *b, size_t words,
+                         unsigned long long *count, hipStream_t s);
 // dist[act[p]] = dist_v[p], assign[act[p]] = assign_v[p]; the centers accepted under
 // the view (labels label_lo .. n_done - 1, n_done read from ctl) get their positions in
 // the shard: hist[l].gidx = goff + act[hist[l].gidx - goff]

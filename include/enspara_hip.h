@@ -286,6 +286,16 @@ int ek_ti_stats(ek_ctx *ctx, int64_t *tiles, int64_t *skipped);
  * [1] frames x rounds streamed, [2] frames x rounds left out, [3] views ended by
  * their guard (the maximum fell to it before the run stopped). */
 int ek_view_stats(ek_ctx *ctx, int64_t *stats);
+/* TEST entry.  Selects the frames whose distance is above theta, builds their view as a
+ * rebuild does (into buffers filled with 0xFF bytes; the frame-minor tiles on demand
+ * from the quad copy where the context has one) and, in scratch of its own, the same
+ * layouts by the earlier path (gather -> frame-minor tiles -> quad copy), and
+ * compares on the device word for word: out[0] frames in the view, out[1] words of the
+ * quad copy that differ (whole tiles, padding included; 0 without a quad copy), out[2]
+ * words of the frame-minor tiles, out[3] words of the frame-major copy, traces,
+ * distances and labels of the live frames.  Not during a run; the run state is left
+ * as it was. */
+int ek_view_layout_check(ek_ctx *ctx, float theta, int64_t *out);
 
 /* history written by ek_kcenters_step: for labels [first, first+count) the
  * global frame index and pre-update distance of each accepted center;
@@ -977,9 +987,18 @@ enum ek_option {
      * 2 theta, and their results are scattered back.  Centers, labels and distances
      * are unchanged.  0 never, 1 (default) when the view would stream at most 0.8 x
      * the frames streamed now, 2 forced: rebuilt every other round whenever a frame is
-     * settled (tests).  Off with EK_OPT_TRIANGLE, an uploaded state, fewer than 3
+     * settled (tests), 3 as 2 with the view's buffers filled with 0xFF bytes before
+     * every rebuild (tests: a slot a rebuild fails to write is a NaN, not a lucky
+     * zero).  Off with EK_OPT_TRIANGLE, an uploaded state, fewer than 3
      * atoms, or no memory for the second store. */
-    EK_OPT_ACTIVE_VIEW = 24
+    EK_OPT_ACTIVE_VIEW = 24,
+    /* the active view's policy, in per mille, 500 .. 950 each.  EK_OPT_VIEW_RHO
+     * (default 750): a view's guard sits at this share of the maximum it was built
+     * at; every value is sound (the guard is derived from theta).  EK_OPT_VIEW_RATIO
+     * (default 800): a view is built when it would stream at most this share of the
+     * frames streamed now. */
+    EK_OPT_VIEW_RHO = 25,
+    EK_OPT_VIEW_RATIO = 26
 };
 int ek_set_option(ek_ctx *ctx, int32_t key, int32_t value);
 /* the value an option holds (what ek_set_option stored, or its default) */

@@ -51,6 +51,10 @@ SYMBOLS = [
     "ek_tpt_committors", "ek_tpt_mfpts_sinks", "ek_tpt_mfpts_all", "ek_tpt_fluxes",
     "ek_mi_open", "ek_mi_add", "ek_mi_load_counts", "ek_mi_counts", "ek_mi_information",
     "ek_mi_last_timing", "ek_mi_close",
+    "ek_cards_open", "ek_cards_add", "ek_cards_stats", "ek_cards_disorder",
+    "ek_cards_disorder_codes", "ek_cards_matrices", "ek_cards_counts",
+    "ek_cards_last_timing", "ek_cards_close", "ek_cards_scan_chunk",
+    "ek_rotamer_states", "ek_dihedral_angles", "ek_dihedral_rotamers",
     "ek_krylov_create", "ek_krylov_destroy", "ek_krylov_set_vector",
     "ek_krylov_get_vector", "ek_krylov_step", "ek_krylov_rotate",
     "ek_krylov_combine", "ek_krylov_expand", "ek_krylov_set_filter",
@@ -242,6 +246,22 @@ def load():
     L.ek_mi_information.argtypes = [vp, f64p]
     L.ek_mi_last_timing.argtypes = [vp, f64p]
     L.ek_mi_close.argtypes = [vp]
+    L.ek_cards_open.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+    L.ek_cards_add.argtypes = [vp, u8p, i64]
+    L.ek_cards_stats.argtypes = [vp, i64p]
+    L.ek_cards_disorder.argtypes = [vp, i64p, i64p]
+    L.ek_cards_disorder_codes.argtypes = [vp, i32, u8p]
+    L.ek_cards_matrices.argtypes = [vp, f64p]
+    L.ek_cards_counts.argtypes = [vp, i32, u32p]
+    L.ek_cards_last_timing.argtypes = [vp, f64p]
+    L.ek_cards_close.argtypes = [vp]
+    L.ek_cards_scan_chunk.argtypes = []
+    L.ek_cards_scan_chunk.restype = C.c_int
+    L.ek_rotamer_states.argtypes = [C.c_int, f32p, i64, i32, u8p, i32, i32p, f64p, f32p,
+                                    C.c_double, u8p, f64p]
+    L.ek_dihedral_angles.argtypes = [C.c_int, f32p, i64, i32, i32p, i32, f32p, f64p]
+    L.ek_dihedral_rotamers.argtypes = [C.c_int, f32p, i64, i32, i32p, i32, u8p, i32, i32p,
+                                       f64p, f32p, C.c_double, u8p, f32p, f64p]
     L.ek_krylov_create.argtypes = [C.c_int, i64, i64p, i32p, f64p, i32,
                                    C.POINTER(vp)]
     L.ek_krylov_destroy.argtypes = [vp]
@@ -320,3 +340,11 @@ def f64p(a):
 
 def i64p(a):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def u8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))

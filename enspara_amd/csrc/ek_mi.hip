@@ -27,6 +27,7 @@
 // frames in the same lane group and byte, and the sum over frames has no order.
 // C/D: column l & 15, row 4 (l >> 4) + register.
 #include "ek_common.h"
+#include "ek_mi_launch.h"
 
 #include <new>
 
@@ -44,12 +45,7 @@ extern int ek_set_error(int code, const char *fmt, ...);
 
 #define MI_WG 256
 #define MI_TW 4                 // tiles of 16 per wave and side
-#define MI_BLOCK 128            // rows / columns of a workgroup: 2 x 2 waves
-#define MI_CHUNK 16384          // frames of a workgroup (enspara_amd.info_theory.MI_CHUNK)
-#define MI_PAD 255              // the code of a padding frame: no state (n <= 255)
-#define MI_MAX_STATES 255
-#define MI_MAX_GRID_Z 65535
-#define MI_MAX_FEATURES (MI_MAX_GRID_Z * 64)   // the pack kernel takes 64 features per grid.y
+// (MI_BLOCK, MI_CHUNK, MI_PAD and the limits: ek_mi_launch.h)
 
 typedef int mi_v4i __attribute__((ext_vector_type(4)));
 
@@ -255,8 +251,37 @@ mi_info_kernel(const uint32_t *__restrict__ jc, int64_t pairs, int32_t nx, int32
     mi[p] = acc;
 }
 
+// ---- launches (ek_mi_launch.h) -----------------------------------------------------------------
+void ek_mi_launch_pack(const uint8_t *in, int64_t frames, int32_t F, int64_t tpad, uint8_t *out,
+                       hipStream_t s)
+{
+    hipLaunchKernelGGL(mi_pack_kernel, dim3((unsigned)(tpad / 64), (F + 63) / 64), dim3(MI_WG),
+                       0, s, in, frames, F, tpad, out);
+}
+
+void ek_mi_launch_count(const uint8_t *cx, const uint8_t *cy, int64_t tpad, int32_t fx,
+                        int32_t fy, int32_t nx, int32_t ny, uint32_t *jc, hipStream_t s)
+{
+    const int32_t M = fx * nx, N = fy * ny;
+    const int64_t chunks = (tpad + MI_CHUNK - 1) / MI_CHUNK;
+    for (int64_t z0 = 0; z0 < chunks; z0 += MI_MAX_GRID_Z) {
+        const int64_t nz = (chunks - z0 < MI_MAX_GRID_Z) ? chunks - z0 : MI_MAX_GRID_Z;
+        hipLaunchKernelGGL(mi_count_kernel,
+                           dim3((N + MI_BLOCK - 1) / MI_BLOCK, (M + MI_BLOCK - 1) / MI_BLOCK,
+                                (unsigned)nz),
+                           dim3(MI_WG), 0, s, cx, cy, tpad, fy, nx, ny, M, N, z0, jc);
+    }
+}
+
+void ek_mi_launch_info(const uint32_t *jc, int64_t pairs, int32_t nx, int32_t ny, uint32_t *col,
+                       double *mi, hipStream_t s)
+{
+    hipLaunchKernelGGL(mi_info_kernel, dim3((unsigned)((pairs + MI_WG - 1) / MI_WG)),
+                       dim3(MI_WG), 0, s, jc, pairs, nx, ny, col, mi);
+}
+
 // ---- host ------------------------------------------------------------------------------------
-static int mi_check_memory(size_t bytes, const char *who)
+int ek_mi_check_memory(size_t bytes, const char *who)
 {
     size_t free_b = 0, total_b = 0;
     hipError_t e = hipMemGetInfo(&free_b, &total_b);
@@ -266,6 +291,19 @@ static int mi_check_memory(size_t bytes, const char *who)
     if (bytes + slack > free_b)
         return ek_set_error(EK_ENOMEM, "%s: %zu MiB of device memory are needed, %zu MiB are "
                                        "free", who, bytes >> 20, free_b >> 20);
+    return EK_OK;
+}
+
+int ek_mi_check_shape(int32_t fx, int32_t fy, int32_t nx, int32_t ny, const char *who)
+{
+    if (fx < 1 || fy < 1 || nx < 1 || ny < 1 || nx > MI_MAX_STATES || ny > MI_MAX_STATES)
+        return ek_set_error(EK_EARG, "%s: bad argument (features >= 1, 1 <= states <= %d)",
+                            who, MI_MAX_STATES);
+    if (fx > MI_MAX_FEATURES || fy > MI_MAX_FEATURES)
+        return ek_set_error(EK_EARG, "%s: at most %d features a side", who, MI_MAX_FEATURES);
+    if ((int64_t)fx * nx > INT32_MAX - MI_BLOCK || (int64_t)fy * ny > INT32_MAX - MI_BLOCK ||
+        ((int64_t)fx * nx + MI_BLOCK - 1) / MI_BLOCK > MI_MAX_GRID_Z)
+        return ek_set_error(EK_EARG, "%s: features x states is too large", who);
     return EK_OK;
 }
 
@@ -303,15 +341,9 @@ extern "C" int ek_mi_open(int device, int32_t fx, int32_t fy, int32_t nx, int32_
     if (!out)
         return ek_set_error(EK_EARG, "ek_mi_open: null output");
     *out = nullptr;
-    if (fx < 1 || fy < 1 || nx < 1 || ny < 1 || nx > MI_MAX_STATES || ny > MI_MAX_STATES)
-        return ek_set_error(EK_EARG, "ek_mi_open: bad argument (features >= 1, 1 <= states "
-                                     "<= %d)", MI_MAX_STATES);
-    if (fx > MI_MAX_FEATURES || fy > MI_MAX_FEATURES)
-        return ek_set_error(EK_EARG, "ek_mi_open: at most %d features a side",
-                            MI_MAX_FEATURES);
-    if ((int64_t)fx * nx > INT32_MAX - MI_BLOCK || (int64_t)fy * ny > INT32_MAX - MI_BLOCK ||
-        ((int64_t)fx * nx + MI_BLOCK - 1) / MI_BLOCK > MI_MAX_GRID_Z)
-        return ek_set_error(EK_EARG, "ek_mi_open: features x states is too large");
+    rc = ek_mi_check_shape(fx, fy, nx, ny, "ek_mi_open");
+    if (rc != EK_OK)
+        return rc;
     {
         hipError_t e0 = hipSetDevice(device);
         if (e0 != hipSuccess)
@@ -327,7 +359,7 @@ extern "C" int ek_mi_open(int device, int32_t fx, int32_t fy, int32_t nx, int32_
     h->nx = nx;
     h->ny = ny;
     h->cells = (size_t)fx * fy * nx * ny;
-    rc = mi_check_memory(h->cells * sizeof(uint32_t), "ek_mi_open");
+    rc = ek_mi_check_memory(h->cells * sizeof(uint32_t), "ek_mi_open");
     if (rc != EK_OK)
         goto done;
     MI_HIP(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
@@ -359,16 +391,14 @@ extern "C" int ek_mi_add(ek_mi *h, const uint8_t *X, const uint8_t *Y, int64_t f
     if (frames == 0)
         return EK_OK;
 
-    const int64_t tpad = (frames + 63) / 64 * 64;
+    const int64_t tpad = ek_mi_tpad(frames);
     const int32_t fmax = h->fx > h->fy ? h->fx : h->fy;
     const size_t raw_b = (size_t)frames * fmax;
     const size_t cx_b = (size_t)h->fx * tpad, cy_b = Y ? (size_t)h->fy * tpad : 0;
-    const int32_t M = h->fx * h->nx, N = h->fy * h->ny;
-    const int64_t chunks = (tpad + MI_CHUNK - 1) / MI_CHUNK;
     uint8_t *d_raw = nullptr, *d_cx = nullptr, *d_cy = nullptr;
     float ms = 0.f;
 
-    rc = mi_check_memory(raw_b + cx_b + cy_b, "ek_mi_add");
+    rc = ek_mi_check_memory(raw_b + cx_b + cy_b, "ek_mi_add");
     if (rc != EK_OK)
         return rc;
     MI_HIP(hipMalloc((void **)&d_raw, raw_b));
@@ -377,22 +407,13 @@ extern "C" int ek_mi_add(ek_mi *h, const uint8_t *X, const uint8_t *Y, int64_t f
         MI_HIP(hipMalloc((void **)&d_cy, cy_b));
     MI_HIP(hipEventRecord(h->ev[0], h->s));
     MI_HIP(hipMemcpyAsync(d_raw, X, (size_t)frames * h->fx, hipMemcpyHostToDevice, h->s));
-    hipLaunchKernelGGL(mi_pack_kernel, dim3((unsigned)(tpad / 64), (h->fx + 63) / 64),
-                       dim3(MI_WG), 0, h->s, d_raw, frames, h->fx, tpad, d_cx);
+    ek_mi_launch_pack(d_raw, frames, h->fx, tpad, d_cx, h->s);
     if (Y) {
         MI_HIP(hipMemcpyAsync(d_raw, Y, (size_t)frames * h->fy, hipMemcpyHostToDevice, h->s));
-        hipLaunchKernelGGL(mi_pack_kernel, dim3((unsigned)(tpad / 64), (h->fy + 63) / 64),
-                           dim3(MI_WG), 0, h->s, d_raw, frames, h->fy, tpad, d_cy);
+        ek_mi_launch_pack(d_raw, frames, h->fy, tpad, d_cy, h->s);
     }
     MI_HIP(hipEventRecord(h->ev[1], h->s));
-    for (int64_t z0 = 0; z0 < chunks; z0 += MI_MAX_GRID_Z) {
-        const int64_t nz = (chunks - z0 < MI_MAX_GRID_Z) ? chunks - z0 : MI_MAX_GRID_Z;
-        hipLaunchKernelGGL(mi_count_kernel,
-                           dim3((N + MI_BLOCK - 1) / MI_BLOCK, (M + MI_BLOCK - 1) / MI_BLOCK,
-                                (unsigned)nz),
-                           dim3(MI_WG), 0, h->s, d_cx, Y ? d_cy : d_cx, tpad, h->fy, h->nx,
-                           h->ny, M, N, z0, h->jc);
-    }
+    ek_mi_launch_count(d_cx, Y ? d_cy : d_cx, tpad, h->fx, h->fy, h->nx, h->ny, h->jc, h->s);
     MI_HIP(hipEventRecord(h->ev[2], h->s));
     MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(h->s));
@@ -450,15 +471,14 @@ extern "C" int ek_mi_information(ek_mi *h, double *mi_out)
     uint32_t *d_col = nullptr;
     double *d_mi = nullptr;
     float ms = 0.f;
-    rc = mi_check_memory((size_t)pairs * (h->ny * sizeof(uint32_t) + sizeof(double)),
+    rc = ek_mi_check_memory((size_t)pairs * (h->ny * sizeof(uint32_t) + sizeof(double)),
                          "ek_mi_information");
     if (rc != EK_OK)
         return rc;
     MI_HIP(hipMalloc((void **)&d_col, (size_t)pairs * h->ny * sizeof(uint32_t)));
     MI_HIP(hipMalloc((void **)&d_mi, (size_t)pairs * sizeof(double)));
     MI_HIP(hipEventRecord(h->ev[0], h->s));
-    hipLaunchKernelGGL(mi_info_kernel, dim3((unsigned)((pairs + MI_WG - 1) / MI_WG)),
-                       dim3(MI_WG), 0, h->s, h->jc, pairs, h->nx, h->ny, d_col, d_mi);
+    ek_mi_launch_info(h->jc, pairs, h->nx, h->ny, d_col, d_mi, h->s);
     MI_HIP(hipEventRecord(h->ev[3], h->s));
     MI_HIP(hipGetLastError());
     MI_HIP(hipMemcpyAsync(mi_out, d_mi, (size_t)pairs * sizeof(double), hipMemcpyDeviceToHost,

@@ -1,3 +1,6 @@
 """Geometry helpers on the hot path: point-vs-set distances in feature space
-(reference enspara/geometry/libdist.pyx)."""
+(reference enspara/geometry/libdist.pyx), dihedral angles and buffered rotamer
+states (reference enspara/geometry/rotamer.py)."""
 from . import libdist  # noqa: F401
+from . import rotamer  # noqa: F401
+from .rotamer import all_rotamers  # noqa: F401

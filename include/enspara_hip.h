@@ -649,6 +649,81 @@ int ek_mi_information(ek_mi *h, double *mi_out);
 int ek_mi_last_timing(ek_mi *h, double *ms_out);
 int ek_mi_close(ek_mi *h);
 
+/* ---- CARDS: transition statistics, disorder codes, four mutual-information matrices --
+ * Replaces enspara/cards/disorder.py and the four mi_matrix calls of cards.py (csrc/
+ * ek_cards.hip).  A handle keeps the rotamer codes S and the disorder codes D of every
+ * trajectory added to it on the device, in ek_mi's packed layout; f features of
+ * n_states <= 255 states each.  All arrays are host memory.
+ * ek_cards_open: EK_EARG on ek_mi_open's limits, EK_ENOMEM if the four count arrays
+ * ([f][f][n][n], [f][f][2][2], [f][f][n][2], [f][f][2][n] uint32) do not fit.
+ * ek_cards_add: X [frames][f] state codes as bytes (the caller validates them), 1 <=
+ * frames < 2^26, the frames of all calls below 2^32 (EK_EARG); uploads, packs, keeps
+ * the codes and computes the trajectory's statistics.  EK_ENOMEM if the resident codes
+ * (2 f frames bytes) do not fit.
+ * ek_cards_stats: out [trajectories][f][4] int64 = (n, first, last, s2) per trajectory
+ * and feature: the number of transitions (X[t] != X[t + 1], t + 1 < frames), the first
+ * and the last transition frame and s2 = the sum of w (w + 1) / 2 over the waiting times
+ * w = [first, differences ...]; without a transition (0, -1, -1, 0).
+ * ek_cards_disorder: lo, hi [f] int64; D[t][j] = 1 exactly where neighbouring
+ * transitions a < b of feature j exist with a <= t < b and lo[j] <= b - a <= hi[j], 0
+ * elsewhere (before the first transition, from the last one on).
+ * ek_cards_disorder_codes: out [frames][f] uint8 of trajectory `traj` (EK_ESTATE before
+ * ek_cards_disorder).
+ * ek_cards_matrices: mi_out [4][f][f] float64 = the mutual information (as
+ * ek_mi_information's, not normalised) of S-S, D-D, S-D and D-S over all trajectories;
+ * the D-S counts are the integer transpose of the S-D counts.  ek_cards_counts downloads
+ * the counts of matrix `which` (0 .. 3) afterwards.
+ * ek_cards_last_timing: ms_out[8] between HIP events = the last add's upload and pack,
+ * its statistics kernels, the last ek_cards_disorder's kernels, and of the last
+ * ek_cards_matrices the S-S, D-D and S-D count passes, the transpose, the four
+ * information kernels.  ek_cards_scan_chunk: the frames of one scan chunk. */
+typedef struct ek_cards ek_cards;
+int ek_cards_open(int device, int32_t f, int32_t n_states, ek_cards **out);
+int ek_cards_add(ek_cards *h, const uint8_t *X, int64_t frames);
+int ek_cards_stats(ek_cards *h, int64_t *stats_out);
+int ek_cards_disorder(ek_cards *h, const int64_t *lo, const int64_t *hi);
+int ek_cards_disorder_codes(ek_cards *h, int32_t traj, uint8_t *out);
+int ek_cards_matrices(ek_cards *h, double *mi_out);
+int ek_cards_counts(ek_cards *h, int32_t which, uint32_t *jc_out);
+int ek_cards_last_timing(ek_cards *h, double *ms_out);
+int ek_cards_close(ek_cards *h);
+int ek_cards_scan_chunk(void);
+
+/* ---- dihedral angles and buffered rotamer states ------------------------------------
+ * Replaces enspara/geometry/rotamer.py (csrc/ek_rotamer.hip).  All arrays are host
+ * memory.  A dihedral is of one of n_kinds kinds (kind [n] bytes); kind k has
+ * n_basins[k] <= 8 basins with the boundaries hb[k][0 .. n_basins[k]] (hb [n_kinds][9]
+ * float64, from 0 to 360, increasing) and the shift shift[k]; width is the buffer on
+ * either side of a boundary, in [0, 360 / n_basins) (EK_EARG otherwise).
+ * ek_rotamer_states: angles [frames][n] float32, degrees in [0, 360) (the caller
+ * validates) -> states_out [frames][n] uint8.  a = angle - shift in float32, + 360 where
+ * negative; frame 0 takes the basin a lies in (hb[i] <= a < hb[i + 1]; an a that rounds
+ * to 360 counts as the last basin); a later frame keeps the current basin s unless a has
+ * left its gates (lower = hb[s], 0 read as 360, minus width; upper = hb[s + 1], 360 read
+ * as 0, plus width; upper < lower: upper <= a <= lower leaves; upper > lower: anything
+ * outside lower <= a <= upper leaves; equal: never), then takes the basin a lies in.
+ * Compared in float64.
+ * ek_dihedral_angles: xyz [frames][atoms][3] float32, quads [n][4] atom indices (EK_EARG
+ * out of range) -> angles_out [frames][n] float32: atan2((b1 . c1) |b2|, c1 . c2) with b1
+ * = x1 - x0, b2 = x2 - x1, b3 = x3 - x2, c1 = b2 x b3, c2 = b1 x b2 in float32, in
+ * degrees, + 360 where negative, 359.5 where above it.
+ * ek_dihedral_rotamers: both in one pass over the coordinates, the states equal to
+ * ek_rotamer_states of ek_dihedral_angles bit for bit; angles_out may be null.
+ * ms_out (may be null) [2]: the dihedral kernel alone, the state scan, between HIP
+ * events.  At most 2^27 frames a call (EK_EARG); EK_ENOMEM if the arrays do not fit the
+ * device. */
+int ek_rotamer_states(int device, const float *angles, int64_t frames, int32_t n,
+                      const uint8_t *kind, int32_t n_kinds, const int32_t *n_basins,
+                      const double *hb, const float *shift, double width,
+                      uint8_t *states_out, double *ms_out);
+int ek_dihedral_angles(int device, const float *xyz, int64_t frames, int32_t atoms,
+                       const int32_t *quads, int32_t n, float *angles_out, double *ms_out);
+int ek_dihedral_rotamers(int device, const float *xyz, int64_t frames, int32_t atoms,
+                         const int32_t *quads, int32_t n, const uint8_t *kind,
+                         int32_t n_kinds, const int32_t *n_basins, const double *hb,
+                         const float *shift, double width, uint8_t *states_out,
+                         float *angles_out, double *ms_out);
+
 /* ---- leading eigenpairs of a sparse transition matrix ---------------------------
  * Device primitives of an Arnoldi / Krylov-Schur solver replacing the ARPACK /
  * LAPACK calls of eigenspectrum (enspara/msm/transition_matrices.py:173-233).

@@ -54,6 +54,8 @@ SYMBOLS = [
     "ek_cards_open", "ek_cards_add", "ek_cards_stats", "ek_cards_disorder",
     "ek_cards_disorder_codes", "ek_cards_matrices", "ek_cards_counts",
     "ek_cards_last_timing", "ek_cards_close", "ek_cards_scan_chunk",
+    "ek_sasa_open", "ek_sasa_run", "ek_sasa_last_timing", "ek_sasa_close",
+    "ek_wmi_run", "ek_wmi_last_timing",
     "ek_rotamer_states", "ek_dihedral_angles", "ek_dihedral_rotamers",
     "ek_krylov_create", "ek_krylov_destroy", "ek_krylov_set_vector",
     "ek_krylov_get_vector", "ek_krylov_step", "ek_krylov_rotate",
@@ -257,6 +259,12 @@ def load():
     L.ek_cards_close.argtypes = [vp]
     L.ek_cards_scan_chunk.argtypes = []
     L.ek_cards_scan_chunk.restype = C.c_int
+    L.ek_sasa_open.argtypes = [C.c_int, i32, f32p, i32, f32p, i32, i32p, i32p, C.POINTER(vp)]
+    L.ek_sasa_run.argtypes = [vp, f32p, i64, i64, i32p, f32p, f32p]
+    L.ek_sasa_last_timing.argtypes = [vp, f64p]
+    L.ek_sasa_close.argtypes = [vp]
+    L.ek_wmi_run.argtypes = [C.c_int, u8p, f64p, i64, i32, i32, f64p, f64p]
+    L.ek_wmi_last_timing.argtypes = [f64p]
     L.ek_rotamer_states.argtypes = [C.c_int, f32p, i64, i32, u8p, i32, i32p, f64p, f32p,
                                     C.c_double, u8p, f64p]
     L.ek_dihedral_angles.argtypes = [C.c_int, f32p, i64, i32, i32p, i32, f32p, f64p]

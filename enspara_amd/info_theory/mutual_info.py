@@ -36,7 +36,15 @@ Where this differs from the reference, on purpose:
   same wherever ``n_x`` and ``n_y`` are equal or plain integers, an error for a
   matrix that is not square, and the other feature's capacity for a square one
   with unequal state vectors.
-* ``weighted_mi`` is absent.
+* ``weighted_mi`` (csrc/ek_wmi.hip) raises ``DataInvalid`` where the reference
+  asserts (negative weights, weights that sum to zero, arrays of the wrong
+  rank), for weights that are not finite, for a code outside ``[0, n)`` of its
+  own feature and for more than ``MAX_STATES`` states.  Its joint probabilities
+  are float64 sums over the frames on the matrix cores, in a fixed order (the
+  same bits every run) that is not numpy's: within ``frames * 2^-52`` relative
+  of the exact sum.  The marginals are the same sums (``P[i, i, u, u]``).
+  The default numbers of states are int64 where the reference's are int16,
+  which makes numpy take the channel capacity's logarithm in float32.
 """
 import logging
 import numbers
@@ -50,10 +58,14 @@ logger = logging.getLogger(__name__)
 
 __all__ = ["mi_matrix", "mi_matrix_serial", "joint_counts", "mutual_information",
            "mi_to_nmi_apc", "deconvolute_network", "mi_to_nmi", "mi_to_apc",
-           "channel_capacity_normalization", "check_features_states", "JointCounts"]
+           "channel_capacity_normalization", "check_features_states", "JointCounts",
+           "weighted_joint_probabilities", "weighted_mi", "weighted_mi_last_timing"]
 
 # frames one workgroup of the count kernel takes (MI_CHUNK of csrc/ek_mi.hip)
 MI_CHUNK = 16384
+# frames of one chunk of the weighted product, up to 64 chunks (WMI_CHUNK of
+# csrc/ek_wmi.hip; longer input is cut into 64 longer chunks)
+WMI_CHUNK = 2048
 # states per feature (MI_MAX_STATES of csrc/ek_mi.hip)
 MAX_STATES = 255
 # features of one side (MI_MAX_FEATURES of csrc/ek_mi.hip: the pack kernel's grid)
@@ -366,6 +378,132 @@ def mi_matrix_serial(states_a_list, states_b_list, n_a_states, n_b_states,
     if normalize:
         mi = channel_capacity_normalization(mi, n_a_states, n_b_states)
     return mi
+
+
+# ---- weighted frames ----------------------------------------------------------------
+def _weighted_args(features, weights):
+    """-> (features [T, F] integers, weights [T] float64, checked as the
+    reference asserts)"""
+    features, weights = np.asarray(features), np.array(weights, dtype=np.float64)
+    if features.ndim != 2:
+        raise exception.DataInvalid(
+            "features is [observations, features], not %s" % (features.shape,))
+    if weights.ndim != 1:
+        raise exception.DataInvalid("weights is [observations], not %s" % (weights.shape,))
+    if features.dtype == np.bool_:
+        features = features.astype(np.uint8)
+    if weights.shape[0] != features.shape[0]:
+        raise exception.DataInvalid(
+            "The number of features (%s in array with shape %s) didn't match "
+            "the number of weights (%s)" %
+            (features.shape[0], features.shape, weights.shape[0]))
+    if features.shape[0] < 1 or features.shape[1] < 1:
+        raise exception.DataInvalid("features of shape %s are empty." % (features.shape,))
+    if not np.all(np.isfinite(weights)) or np.any(weights < 0):
+        raise exception.DataInvalid("Weights must be finite and not negative.")
+    if not weights.sum() > 0:
+        raise exception.DataInvalid("Weights must not sum to zero.")
+    return features, weights
+
+
+def _weighted_run(features, weights, n_states, want_P, want_mi, device):
+    S = _n_states(n_states, "the number of states")
+    codes = _codes(features, S, "features")
+    T, F = codes.shape
+    if T >= MAX_FRAMES or F > MAX_FEATURES:
+        raise exception.DataInvalid(
+            "No support for %d frames x %d features (fewer than %d frames, at most %d "
+            "features)." % (T, F, MAX_FRAMES, MAX_FEATURES))
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    P = np.zeros((F, F, S, S)) if want_P else None
+    mi = np.zeros((F, F)) if want_mi else None
+    _check(_lib.load().ek_wmi_run(int(device), _u8p(codes), _lib.f64p(weights), T, F, S,
+                                  None if P is None else _lib.f64p(P),
+                                  None if mi is None else _lib.f64p(mi)))
+    return P, mi
+
+
+def weighted_joint_probabilities(features, weights, n_states, device=0):
+    """Joint probabilities of weighted observations.
+
+    Parameters
+    ----------
+    features : np.ndarray, shape=(n_observations, n_features), bool or integers
+        State of every feature in every observation, in ``[0, n_states)``.
+    weights : np.ndarray, shape=(n_observations,)
+        Weight of each observation; used as given (not normalised).
+    n_states : int
+        Number of states of every feature.
+
+    Returns
+    -------
+    P : np.ndarray, shape=(n_features, n_features, n_states, n_states), float64
+        ``P[i, j, u, v]`` = the sum of the weights of the observations with
+        feature i in state u and feature j in state v (``joint_counts``'
+        layout).
+    """
+    features, weights = _weighted_args(features, weights)
+    return _weighted_run(features, weights, n_states, True, False, device)[0]
+
+
+def weighted_mi(features, weights, n_feature_states=None, normalize=True, device=0):
+    """Compute a mutual information matrix using weighted observations.
+
+    The marginal and joint probability distributions P(x), P(y) and P(x, y)
+    of every pair of features are sums of the observations' weights.
+
+    Parameters
+    ----------
+    features : np.ndarray, shape=(n_observations, n_features), bool or integers
+        Observations of multiple variables (features) between which to
+        compute the pairwise mutual information.
+    weights : np.ndarray, shape=(n_observations,)
+        Probability distribution across observations; divided by its sum
+        (L1 norm) if that is not 1.
+    n_feature_states : np.ndarray, shape=(n_features,), default=None
+        The number of states each feature can take on (used for
+        normalization).  If None, ``features.max() + 1`` for every feature.
+    normalize : bool, default=True
+        Normalize by channel capacity.
+
+    Returns
+    -------
+    mi : np.ndarray, shape=(n_features, n_features), float64
+        Cell i, j is the mutual information between features i and j, not
+        below 0.
+    """
+    features, weights = _weighted_args(features, weights)
+    if weights.sum() != 1:
+        weights = weights / np.linalg.norm(weights, ord=1)
+    if n_feature_states is None:
+        n_feature_states = np.full(features.shape[1], int(features.max()) + 1, dtype=np.int64)
+    else:
+        n_feature_states = np.array(n_feature_states)
+    if n_feature_states.ndim != 1 or n_feature_states.shape[0] != features.shape[1]:
+        raise exception.DataInvalid(
+            "The length of feature states number vector (%s) must equal the"
+            "number of features given (%s)" % (
+                n_feature_states.shape[0] if n_feature_states.ndim else "scalar",
+                features.shape[1]))
+    if not np.issubdtype(n_feature_states.dtype, np.integer):
+        raise exception.DataInvalid(
+            "Numbers of states are integers, not %s." % n_feature_states.dtype)
+    if features.min() < 0 or np.any(features.max(axis=0) >= n_feature_states):
+        raise exception.DataInvalid(
+            "State indices of every feature must lie in [0, n) of its number of states n.")
+    mi = _weighted_run(features, weights, int(n_feature_states.max()), False, True, device)[1]
+    if normalize:
+        mi = channel_capacity_normalization(mi, n_feature_states, n_feature_states)
+    np.clip(mi, a_min=0, a_max=np.inf, out=mi)
+    return mi
+
+
+def weighted_mi_last_timing():
+    """Milliseconds between device events of the last weighted run: upload and
+    pack, product kernel, reduction, information kernel (ek_wmi_last_timing)."""
+    ms = np.zeros(4)
+    _check(_lib.load().ek_wmi_last_timing(_lib.f64p(ms)))
+    return ms
 
 
 # ---- [F, F] work on the host ------------------------------------------------------

@@ -689,6 +689,51 @@ int ek_cards_last_timing(ek_cards *h, double *ms_out);
 int ek_cards_close(ek_cards *h);
 int ek_cards_scan_chunk(void);
 
+/* ---- Shrake-Rupley solvent-accessible surface area -----------------------------------
+ * Replaces mdtraj.shrake_rupley(mode='atom') as enspara/info_theory/exposons.py calls it,
+ * and condense_sidechain_sasas (csrc/ek_sasa.hip).  A handle holds, on the device, R
+ * [atoms] = radius + probe in nm (0 < R <= 4), the n_points <= 4096 sphere points
+ * [n_points][3] and n_groups >= 0 groups of atoms: group g lists group_atoms[
+ * group_offsets[g] .. group_offsets[g + 1]), none empty, every index in [0, atoms)
+ * (EK_EARG otherwise).  All arrays are host memory.
+ * ek_sasa_run: xyz [frames][atoms][3] float32 in nm, finite and within 128 nm of the
+ * origin (EK_EARG).  In float32, nothing fused: p = (R_i * s_k) + x_i per component;
+ * point k of atom i is blocked iff for some j != i (dx*dx + dy*dy) + dz*dz < R_j * R_j
+ * with d = p - x_j; counts_out [frames][atoms] = the points not blocked; areas_out
+ * [frames][atoms] = ((c * R_i) * R_i) * float(count), c = float(4 pi / n_points);
+ * groups_out [frames][n_groups] = 0.0f plus the group's areas in the order listed.
+ * Each output may be null.  Neighbours are culled at r_ij < R_i + R_j + 2^-13 nm, which
+ * under the limits above never changes a count.  chunk_frames > 0: frames
+ * of one upload and launch (at most 32768); 0: what fits half of the free device memory.
+ * ek_sasa_last_timing: ms_out[3] = the last run's uploads, count kernels and group
+ * kernels, summed over its chunks, between HIP events. */
+typedef struct ek_sasa ek_sasa;
+int ek_sasa_open(int device, int32_t atoms, const float *R, int32_t n_points,
+                 const float *points, int32_t n_groups, const int32_t *group_offsets,
+                 const int32_t *group_atoms, ek_sasa **out);
+int ek_sasa_run(ek_sasa *h, const float *xyz, int64_t frames, int64_t chunk_frames,
+                int32_t *counts_out, float *areas_out, float *groups_out);
+int ek_sasa_last_timing(ek_sasa *h, double *ms_out);
+int ek_sasa_close(ek_sasa *h);
+
+/* ---- joint probabilities and mutual information of weighted frames --------------------
+ * Replaces the arithmetic of weighted_mi (enspara/info_theory/mutual_info.py:78-178;
+ * csrc/ek_wmi.hip).  codes [frames][F] state codes as bytes (the caller validates them:
+ * a code >= S counts nowhere), weights [frames] float64 (finite and not negative: the
+ * caller's to check), 1 <= frames < 2^31 - 64, F and S
+ * within ek_mi_open's limits; host memory.  P_out (may be null) [F][F][S][S] float64,
+ * P[i][j][u][v] = the sum over frames of w_t [f_ti == u] [f_tj == v], taken on the
+ * float64 matrix cores per chunk of frames and over the chunks in ascending order: no
+ * atomics, the same bits every run.  mi_out (may be null; not both) [F][F] float64 =
+ * per pair the sum over u (outer) and v (inner) of P * log(P / (P_x[i][u] * P_x[j][v]))
+ * with P_x[i][u] = P[i][i][u][u], terms with P = 0 or P_x * P_x = 0 skipped; not
+ * normalised, not clipped.  EK_ENOMEM if the chunk partials do not fit the device.
+ * ek_wmi_last_timing: ms_out[4] = the last run's upload and pack, product kernel,
+ * reduction, information kernel, between HIP events. */
+int ek_wmi_run(int device, const uint8_t *codes, const double *weights, int64_t frames,
+               int32_t F, int32_t S, double *P_out, double *mi_out);
+int ek_wmi_last_timing(double *ms_out);
+
 /* ---- dihedral angles and buffered rotamer states ------------------------------------
  * Replaces enspara/geometry/rotamer.py (csrc/ek_rotamer.hip).  All arrays are host
  * memory.  A dihedral is of one of n_kinds kinds (kind [n] bytes); kind k has

@@ -1120,957 +1120,6 @@ extern "C" int ek_history_download(ek_ctx *c, int32_t first, int32_t count,
     return EK_OK;
 }
 
-// ---- k-centers rounds, in the form that pays ---------------------------------------
-// A round with T candidates costs more than a one-center step (more FMAs per
-// byte, the small kernels that decide the chain) and accepts between 1 and T
-// centers.  At the very start of a fit the guesses rarely hit -- every new
-// center reshapes the distances of most frames -- and one-center steps are the
-// faster way forward; soon after, nearly every guess is accepted.  Both forms
-// produce the same centers, labels and distances, so the choice is free: every
-// batch is timed on the device (centers per millisecond) and the other form is
-// tried for a short batch at intervals that double while it keeps losing.
-// ---- the active view (ek_view.hip; DESIGN.md 4a "Active view") ---------------------
-// The policy's two numbers are options (EK_OPT_VIEW_RHO, EK_OPT_VIEW_RATIO, per mille):
-// a view's guard sits at rho x the maximum it was built at (frames at up to about half
-// of that are settled), and a view is built when it would stream at most ratio x the
-// frames streamed now.
-static constexpr int EK_VIEW_MIN_ROUNDS = 24;   // rounds left that make a rebuild worth it
-static constexpr int EK_VIEW_BATCH = 16;        // rounds between two looks at the policy
-// The look (ek_view_look_kernel) rides behind the last round of a batch and comes back
-// with the control word.  Looks that find nothing settled pause, as the triangle masks
-// do: 1, 2, 4, 8 batches after an estimate above EK_VIEW_IDLE x the frames streamed;
-// a paused batch may be EK_VIEW_PAUSED_BATCH rounds long.
-static constexpr double EK_VIEW_IDLE = 0.95;
-static constexpr int EK_VIEW_PAUSE_MAX = 8;
-static constexpr int EK_VIEW_PAUSED_BATCH = 4 * EK_VIEW_BATCH;
-static constexpr double EK_VIEW_REL = 1e-3, EK_VIEW_ABS = 1e-3;     // ek_round_ti_*'s margin
-
-void ek_view_free(ek_ctx *c)
-{
-    (void)hipFree(c->v_aos);
-    (void)hipFree(c->v_tiles);
-    (void)hipFree(c->v_qtiles);
-    (void)hipFree(c->v_G);
-    (void)hipFree(c->v_dist);
-    (void)hipFree(c->v_assign);
-    (void)hipFree(c->v_act);
-    (void)hipFree(c->v_blockcnt);
-    (void)hipFree(c->v_blockoff);
-    (void)hipFree(c->v_count);
-    c->v_aos = c->v_tiles = c->v_qtiles = nullptr;
-    c->v_G = nullptr;
-    c->v_dist = nullptr;
-    c->v_assign = nullptr;
-    c->v_act = c->v_blockcnt = c->v_blockoff = c->v_count = nullptr;
-    c->view_cap = 0;
-}
-
-// room for a view of `frames` frames (whole tiles); EK_ENOMEM: there is none, and the
-// context remembers
-static int ek_view_alloc(ek_ctx *c, int64_t frames)
-{
-    const int64_t cap = (frames + EK_TILE - 1) / EK_TILE * EK_TILE;
-    if (c->view_cap >= cap)
-        return EK_OK;
-    EK_HIP(ek_wait(c));
-    ek_view_free(c);
-    const size_t nt = (size_t)(cap / EK_TILE), A3 = (size_t)3 * c->A;
-    const size_t nblk = ek_view_sel_blocks(std::max<int64_t>(c->n, 1));
-    hipError_t e = hipSuccess;
-#define EK_VALLOC(ptr, bytes)                                                  \
-    if (e == hipSuccess)                                                       \
-        e = ek_malloc_named(c, (void **)&(ptr), (bytes), #ptr);
-    EK_VALLOC(c->v_aos, (size_t)cap * A3 * sizeof(float));
-    EK_VALLOC(c->v_tiles, nt * A3 * EK_TILE * sizeof(float));
-    EK_VALLOC(c->v_qtiles, ek_quad_tiles_bytes((int64_t)nt, c->A));
-    EK_VALLOC(c->v_G, (size_t)cap * sizeof(double));
-    EK_VALLOC(c->v_dist, (size_t)cap * sizeof(float));
-    EK_VALLOC(c->v_assign, (size_t)cap * sizeof(int32_t));
-    EK_VALLOC(c->v_act, (size_t)cap * sizeof(uint32_t));
-    EK_VALLOC(c->v_blockcnt, nblk * sizeof(uint32_t));
-    EK_VALLOC(c->v_blockoff, nblk * sizeof(uint32_t));
-    EK_VALLOC(c->v_count, 2 * sizeof(uint32_t));
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->v_count, 0, 2 * sizeof(uint32_t), c->stream);
-#undef EK_VALLOC
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        ek_view_free(c);
-        if (e == hipErrorOutOfMemory) {
-            c->view_nomem = true;
-            return EK_ENOMEM;
-        }
-        EK_HIP(e);
-    }
-    c->view_cap = cap;
-    return EK_OK;
-}
-
-// the store the rounds see: the shard's own, or its active view
-struct EkStore {
-    float *dist;
-    int32_t *assign;
-    const float *tiles, *qtiles, *aos;
-    const double *G;
-    int64_t n, n_pad;
-};
-// a run's view, for the one who has to put it back
-struct EkViewRun {
-    bool on = false;
-    int64_t n = 0;              // frames in it
-    int32_t label_lo = 0;       // centers from this label on carry positions of the view
-    double guard = 0.0;         // no center is accepted at or below it
-    bool tiles_valid = false;   // v_tiles holds this view (built on demand from v_qtiles)
-};
-
-// 0xFF bytes all over the view's buffers (active view 3, ek_view_layout_check)
-static hipError_t ek_view_poison(ek_ctx *c)
-{
-    const size_t cap = (size_t)c->view_cap, nt = cap / EK_TILE, A3 = (size_t)3 * c->A;
-    hipError_t e = hipMemsetAsync(c->v_aos, 0xFF, cap * A3 * sizeof(float), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->v_tiles, 0xFF, nt * A3 * EK_TILE * sizeof(float), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->v_qtiles, 0xFF, ek_quad_tiles_bytes((int64_t)nt, c->A),
-                           c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->v_G, 0xFF, cap * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->v_dist, 0xFF, cap * sizeof(float), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->v_assign, 0xFF, cap * sizeof(int32_t), c->stream);
-    return e;
-}
-
-// the view's store from the selection c->v_act[0 .. n_v): frame-major copy, traces,
-// distances, labels and the quad copy; without a quad copy in the context (rounds of 8
-// at most) the frame-minor tiles instead.  -> whether v_tiles holds the view
-static bool ek_view_build(ek_ctx *c, int64_t n_v)
-{
-    ek_launch_view_build(c->v_act, n_v, c->A, c->qt_valid, c->aos, c->G, c->dist, c->assign,
-                         c->v_aos, c->qt_valid ? c->v_qtiles : c->v_tiles, c->v_G, c->v_dist,
-                         c->v_assign, c->stream);
-    return !c->qt_valid;
-}
-
-static void ek_view_scatter_back(ek_ctx *c, EkViewRun &v)
-{
-    ek_launch_view_scatter(c->v_act, v.n, c->v_dist, c->v_assign, c->dist, c->assign,
-                           c->hist, v.label_lo, c->hist_cap, c->ctl, c->goff, c->stream);
-    v.on = false;
-}
-
-static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
-                            int32_t max_new, double dist_cutoff, int32_t *n_added,
-                            int64_t *center_index_out, float *center_dist_out,
-                            float *final_maxdist, EkViewRun &view);
-
-static int ek_run_rounds(ek_ctx *c, int Tmax, int32_t first_label,
-                         int32_t max_new, double dist_cutoff, int32_t *n_added,
-                         int64_t *center_index_out, float *center_dist_out,
-                         float *final_maxdist)
-{
-    EkViewRun view;
-    const int rc = ek_run_rounds_in(c, Tmax, first_label, max_new, dist_cutoff, n_added,
-                                    center_index_out, center_dist_out, final_maxdist, view);
-    if (rc != EK_OK && view.on) {
-        // an error under a view: distances, labels and history back in the shard's
-        // own space all the same (what is pending stays unapplied, as without a view)
-        ek_view_scatter_back(c, view);
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipGetLastError();
-    }
-    return rc;
-}
-
-static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
-                            int32_t max_new, double dist_cutoff, int32_t *n_added,
-                            int64_t *center_index_out, float *center_dist_out,
-                            float *final_maxdist, EkViewRun &view)
-{
-    int rc = ek_spec_alloc(c);
-    if (rc)
-        return rc;
-    if (!c->evb0) {
-        EK_HIP(hipEventCreate(&c->evb0));
-        EK_HIP(hipEventCreate(&c->evb1));
-    }
-    EkCtl ctlw;
-    memset(&ctlw, 0, sizeof(ctlw));
-    ctlw.n_done = first_label;
-    ctlw.limit = first_label + max_new;
-    EK_HIP(hipMemcpyAsync(c->ctl, &ctlw, sizeof(ctlw), hipMemcpyHostToDevice,
-                          c->stream));
-    EK_HIP(ek_wait(c));
-    for (int m = 0; m < EK_N_FORMS; ++m)
-        c->st_rounds[m] = c->st_centers[m] = 0;
-    c->view_stats[0] = c->view_stats[1] = c->view_stats[2] = c->view_stats[3] = 0;
-    // Triangle inequality (option key 11; reference `use_triangle_inequality`,
-    // kcenters.py:287-296): one center at a time, tiles that cannot change are
-    // not read.  Needs every frame's distance to be the one to the center its
-    // label names (a fresh run) and distances that behave like a metric.
-    const bool tri = c->tri && c->state_exact && first_label == 0 && c->A >= 3;
-    if (tri) {
-        if (first_label + max_new > c->ti_cap) {
-            EK_HIP(ek_wait(c));
-            (void)hipFree(c->ti_D);
-            c->ti_D = nullptr;
-            c->ti_cap = 0;
-            EK_HIP(hipMalloc((void **)&c->ti_D,
-                             (size_t)(first_label + max_new + 1) * sizeof(float)));
-            c->ti_cap = first_label + max_new + 1;
-        }
-        if (!c->ti_skip) {
-            EK_HIP(hipMalloc((void **)&c->ti_skip,
-                             (size_t)std::max<int64_t>(c->n_tiles, 1)));
-            EK_HIP(hipMalloc((void **)&c->ti_stats, 2 * sizeof(unsigned long long)));
-        }
-        EK_HIP(hipMemsetAsync(c->ti_stats, 0, 2 * sizeof(unsigned long long),
-                              c->stream));
-        if (first_label + max_new > c->ti_rtab_cap) {
-            EK_HIP(ek_wait(c));
-            (void)hipFree(c->ti_rtab);
-            c->ti_rtab = nullptr;
-            c->ti_rtab_cap = 0;
-            EK_HIP(hipMalloc((void **)&c->ti_rtab, (size_t)(first_label + max_new + 1) *
-                                                       EK_MAX_CANDS * sizeof(float)));
-            c->ti_rtab_cap = first_label + max_new + 1;
-        }
-        if (!c->ti_tmask)
-            EK_HIP(hipMalloc((void **)&c->ti_tmask,
-                             (size_t)std::max<int64_t>(c->n_tiles, 1) * sizeof(uint32_t)));
-    }
-    c->ti_tiles = c->ti_skipped = 0;
-    // three launches per round (ek_round.hip) when the pieces it is built from
-    // are the ones selected; rounds of 32 exist in that form only
-    const bool fused = c->fused && c->chain == 1;
-    if (Tmax == 32 && !fused)
-        Tmax = EK_LEGACY_CANDS;
-    if (Tmax >= 16) {
-        const int eq = ek_ensure_qtiles(c);
-        if (eq == EK_ENOMEM)
-            Tmax = 8;
-        else if (eq != EK_OK)
-            return eq;
-    }
-    // an explicit request (option key 4 = 4, 8 or 16) pins the wide form
-    const bool adaptive = c->cands == -1 && c->adapt;
-    const int fpl = ek_pick_fpl(c);
-    const int nt = ek_pick_nt(c);
-    // the forms the run moves between, by candidates per pass
-    int ladder[4], n_ladder = 0;
-    // (triangle inequality, round 5: the rounds of 4 .. 32 candidates leave out
-    // the tiles none of their candidates can change -- ek_round_ti_* --, the
-    // one-center steps the tiles the new center cannot.
-    // Round 4 ran one center per pass with the option on, 3.7 x slower than
-    // without it on data where nothing can be left out.)
-    if (adaptive || (tri && Tmax <= 1))
-        ladder[n_ladder++] = 1;
-    if (Tmax > 1) {
-        // (the ladder is 1 / 8 / 16: rounds of 32 run only where the option pins them,
-        // and a pinned form has no ladder -- `adaptive` needs candidates = -1)
-        if (adaptive && Tmax >= 16)
-            ladder[n_ladder++] = 8;
-        ladder[n_ladder++] = Tmax;
-    }
-    int home = 0;               // ladder index of the form being run
-    int form = ladder[0];       // ... its candidates per pass (the probe's while probing)
-    int held = -1;              // form the candidate record(s) were picked for
-    bool probing = false;
-    int probe_up = 1;           // direction of the next probe (they alternate)
-    double rate_home = 0.0;     // centers per ms of the home form
-    int32_t gap = 8;            // centers until another form is tried again
-    int32_t since = 0;          // centers since one last was
-    EkRound R;
-    R.vecs = c->vecs;
-    R.goff = c->goff;
-    R.A = c->A;
-    R.T = Tmax;
-    R.recs = c->recsT;
-    R.plan = c->plan;
-    R.pend = c->pend;
-    R.ord = c->ord;
-    R.blockmax = c->blockmax;
-    R.pm = c->pm;
-    R.fm = c->fine_pick ? c->fm : nullptr;
-    // (the per-prefix maxima in the pass: where they pay -- shards of up to ~half a
-    // million frames: 10 % of a fit at 125 000; at 10^6 the pass's extra instructions
-    // cost what the chain kernel's sweep did, profiles/r06/sweep_ab_*.log)
-    // (R.sweep: with the store, below)
-    R.top = c->top;
-    R.ctile = c->ctile;
-    R.ctrace = c->ctrace;
-    R.hist = c->hist;
-    R.ctl = c->ctl;
-    R.tick = c->tick;
-    R.rows = c->rows;
-    R.vmask = c->vmask;
-    R.ti_tab = tri ? c->ti_rtab : nullptr;
-    R.ti_stats = tri ? c->ti_stats : nullptr;
-    // ---- the store the rounds see (S): the shard's own, or its active view ----------
-    EkStore S;
-    int nb = 0;
-    auto use_store = [&](bool the_view) {
-        if (the_view)
-            S = EkStore{c->v_dist, c->v_assign, c->v_tiles, c->v_qtiles, c->v_aos, c->v_G,
-                        view.n, (view.n + EK_TILE - 1) / EK_TILE * EK_TILE};
-        else
-            S = EkStore{c->dist, c->assign, c->tiles, c->qtiles, c->aos, c->G, c->n,
-                        c->n_pad};
-        nb = (int)((S.n + EK_BLOCK - 1) / EK_BLOCK);
-        R.dist = S.dist;
-        R.assign = S.assign;
-        R.n = S.n;
-        R.n_pad = S.n_pad;
-        R.tiles = S.tiles;
-        R.qtiles = S.qtiles;
-        R.aos = S.aos;
-        R.G = S.G;
-        R.sweep = (fused && (c->pass_sweep == 2 ||
-                             (c->pass_sweep == 1 && S.n <= (int64_t)2048 * EK_TILE))) ? 1 : 0;
-        // (under a view no center is accepted at or below its guard: the stop rule
-        // itself refuses it -- chain walk, plan and step kernel alike)
-        R.cutoff = the_view ? std::max(dist_cutoff, view.guard) : dist_cutoff;
-    };
-    use_store(false);
-    // Active view (option key 24): needs distances that ARE the distance to the center
-    // the label names, a metric, the fused rounds, and the triangle option off (its
-    // kernels read hist[].gidx as positions of old centers)
-    int view_mode = (c->state_exact && c->A >= 3 && fused && !c->tri && !c->view_nomem)
-                        ? c->active_view : 0;
-    const bool forced = view_mode >= 2;
-    const double rho = c->view_rho / 1000.0, shrink = c->view_ratio / 1000.0;
-    bool looked = false;        // the last batch carried a look: look_cnt is its answer
-    uint32_t look_cnt[2] = {0, 0};
-    int look_pause = 0, look_pause_next = 1;        // batches without a look / the next pause
-    // the whole store again: what is pending applied, the view's results scattered
-    auto leave_view = [&](bool &pending_) {
-        if (pending_) {
-            ek_launch_round_flush(R, c->stream);
-            pending_ = false;
-        }
-        ek_view_scatter_back(c, view);
-        use_store(false);
-    };
-    bool pending = false;       // a fused round may have left a chain to apply
-    int ti_pause = 0, ti_pause_next = 2;            // batches without masks / the next pause
-    bool masks_fresh = false;   // ti_tmask describes the plan the next pass will run
-    // How many far frames per label the candidate pick keeps (ek_top_dev.h): 4 suits
-    // frames in clouds around templates, 16 a continuous landscape (round 5: the
-    // walk 1.3e10 -> 2.5e10 pairs/s).  By the yield the rounds show: a batch that
-    // accepts under 65 % of its guesses lets the next batch of the same form try the
-    // other value; it stays if it accepts a tenth more, a look that loses waits twice
-    // as long (80 % and a twentieth cost the ladder on template data 9 % at 125 000
-    // frames: the early rounds of 8 sit just under 80 % there).
-    int cap = c->pick_cap > 0 ? c->pick_cap : 4;
-    const bool cap_adaptive = c->pick_cap <= 0;
-    bool cap_probing = false;
-    int cap_wait = 0, cap_next_wait = 2, cap_form = 0;
-    double cap_yield_home = 0.0;
-    unsigned long long ti_seen[2] = {0, 0};         // the counters at the last look
-    EK_HIP(hipEventRecord(c->ev0, c->stream));
-    EkCtl cr;
-    memset(&cr, 0, sizeof(cr));
-    cr.n_done = first_label;
-    const int32_t goal = first_label + max_new;
-    double per_round = 0.6 * form;  // centers per round of the current wide form
-    int32_t rounds_before = 0;
-    while (cr.n_done < goal) {
-        const int32_t left = goal - cr.n_done;
-        const bool one = form == 1;
-        R.T = form;
-        // (the masks cost two small launches per round; where they leave nothing
-        // out -- frames in no order: the bench's data -- they pause, for twice as
-        // many batches each time a look finds nothing again)
-        const bool masks = tri && fused && form >= 4 && ti_pause == 0;
-        R.tmask = masks ? c->ti_tmask : nullptr;
-        R.pick_cap = cap;
-        // ---- active view: enter, rebuild or stay, by the look the last batch carried ---
-        if (view_mode && looked && std::isfinite(cr.last_max)) {
-            looked = false;
-            // frames at up to theta are settled while centers are accepted above
-            // guard = 2 theta (1 + rel) + abs = rho x the maximum now
-            const double th = (rho * (double)cr.last_max - EK_VIEW_ABS) /
-                              (2.0 * (1.0 + EK_VIEW_REL));
-            float theta = (float)th;
-            if ((double)theta > th)
-                theta = std::nextafterf(theta, 0.f);
-            if (theta > 0.f) {
-                // how many frames a view built now would hold (look_cnt, counted on the
-                // device at the theta of the same maximum): those of this store
-                // above theta (what is pending not applied: a few too many) and, under
-                // a view, the shard's frames outside it that a lower theta lets in
-                // again (the shard's own copy of the view's frames is as old as the
-                // view: every one of them counts there)
-                const int64_t est =
-                    (int64_t)look_cnt[0] +
-                    (view.on ? std::max<int64_t>(0, (int64_t)look_cnt[1] - view.n) : 0);
-                const bool build =
-                    forced ? est < c->n
-                           : ((double)est <= shrink * (double)S.n &&
-                              (double)left >= EK_VIEW_MIN_ROUNDS * std::max(per_round, 1.0));
-                if (!forced) {
-                    if ((double)est > EK_VIEW_IDLE * (double)S.n) {
-                        look_pause = look_pause_next;
-                        look_pause_next = std::min(2 * look_pause_next, EK_VIEW_PAUSE_MAX);
-                    } else if (build || (double)est <= shrink * (double)S.n) {
-                        look_pause_next = 1;
-                    }
-                }
-                if (build) {
-                    if (view.on) {
-                        leave_view(pending);
-                    } else if (pending) {
-                        ek_launch_round_flush(R, c->stream);
-                        pending = false;
-                    }
-                    uint32_t nv = 0;
-                    ek_launch_view_select(c->dist, c->n, theta, c->v_blockcnt,
-                                          c->v_blockoff, c->v_act, c->view_cap, c->v_count,
-                                          c->stream);
-                    EK_CHECK_LAUNCH();
-                    EK_HIP(hipMemcpyAsync(&nv, c->v_count, sizeof(nv),
-                                          hipMemcpyDeviceToHost, c->stream));
-                    EK_HIP(ek_wait(c));
-                    if (nv > 0 && (int64_t)nv < c->n && (int64_t)nv <= c->view_cap) {
-                        view.n = nv;
-                        view.label_lo = cr.n_done;
-                        view.guard = 2.0 * (double)theta * (1.0 + EK_VIEW_REL) + EK_VIEW_ABS;
-                        if (view_mode == 3)
-                            EK_HIP(ek_view_poison(c));
-                        view.tiles_valid = ek_view_build(c, view.n);
-                        EK_CHECK_LAUNCH();
-                        view.on = true;
-                        use_store(true);
-                        EK_HIP(hipMemsetAsync(c->vmask, 0,
-                                              (size_t)(S.n_pad / EK_WAVE) * sizeof(uint32_t),
-                                              c->stream));
-                        c->view_stats[0]++;
-                    }
-                    held = -1;  // the pick in the new space, from a recomputed blockmax
-                }
-            }
-        }
-        looked = false;
-        // (a view's frame-minor tiles are made when a kernel that reads them runs under
-        // it: the rounds of 8, the one-center step and its pick)
-        if (view.on && !view.tiles_valid && form < 16) {
-            ek_launch_view_tiles(c->v_qtiles, S.n_pad / EK_TILE, c->A, c->v_tiles, c->stream);
-            EK_CHECK_LAUNCH();
-            view.tiles_valid = true;
-        }
-        // ---- the record(s) this form starts from -------------------------------------
-        if (held != form) {
-            if (pending) {      // leaving a fused form: the state as it stands
-                ek_launch_round_flush(R, c->stream);
-                pending = false;
-            } else if (held <= 1) {
-                // the step kernel's partials are per FPL frames
-                ek_launch_blockmax(S.dist, S.n, c->blockmax, c->stream);
-            }
-            if (one) {
-                ek_launch_pick(c->blockmax, nb, S.dist, S.tiles, S.G, S.n,
-                               c->A, c->goff, c->recsT, c->ctl, c->stream);
-            } else if (fused) {
-                ek_launch_round_chain(R, 1, c->stream);
-                ek_launch_round_next(R, 1, c->stream);
-                ek_launch_round_ti(R, goal, c->stream);
-                masks_fresh = R.tmask != nullptr;
-            } else {
-                ek_launch_pickT(c->blockmax, nb, S.tiles, S.G, S.assign, c->A,
-                                form, c->goff, c->recsT, c->ctl, c->top,
-                                c->stream);
-            }
-            EK_CHECK_LAUNCH();
-            if (held != form && !one)
-                per_round = 0.6 * form;
-            held = form;
-        }
-        // ---- one batch: steps (one-center form) or rounds ----------------------------
-        // long enough to amortise the host's look at the control word, short
-        // enough to come back when another form is due
-        const int32_t due = adaptive ? std::max(gap - since, 1) : left;
-        int32_t batch;
-        if (one)    // (never past the goal: a step has no limit check of its own)
-            batch = std::min(left, probing ? 4 : std::min(due, 256));
-        else if (probing)
-            batch = 3;
-        else
-            batch = std::max(2, std::min(256, (int32_t)(std::min(left, due) /
-                                                        per_round) + 1));
-        // (the policy of the active view looks at the state between batches; forced
-        // views -- tests -- are rebuilt every other round)
-        if (forced)
-            batch = std::min(batch, 2);
-        else if (view_mode && !one)
-            batch = std::min(batch, look_pause > 0 ? EK_VIEW_PAUSED_BATCH : EK_VIEW_BATCH);
-        EK_HIP(hipEventRecord(c->evb0, c->stream));
-        if (R.tmask && !masks_fresh) {  // (after a pause: the masks of the plan at hand)
-            ek_launch_round_ti(R, goal, c->stream);
-            masks_fresh = true;
-        }
-        if (!R.tmask)
-            masks_fresh = false;        // (this batch's rounds do not make any)
-        for (int32_t r = 0; r < batch; ++r) {
-            if (one) {
-                const int label = cr.n_done + r;
-                const bool skip = tri && label >= 1;
-                if (skip)
-                    ek_launch_ti(S.aos, S.G, c->A, c->hist, label, c->goff,
-                                 c->recsT, c->ti_D, S.dist, S.assign, S.n,
-                                 c->ctl, c->ti_skip, c->ti_stats, c->stream);
-                ek_launch_step(fpl, 0, nt, S.tiles, S.G, S.dist, S.assign,
-                               c->scratch, c->recsT, 1, S.n, c->A, label,
-                               R.cutoff, c->blockmax, c->hist, c->ctl, c->stream,
-                               skip ? c->ti_skip : nullptr);
-                ek_launch_pick(c->blockmax, ek_step_blocks(fpl, S.n), S.dist,
-                               S.tiles, S.G, S.n, c->A, c->goff, c->recsT,
-                               c->ctl, c->stream);
-                EK_CHECK_LAUNCH();
-                continue;
-            }
-            // sampled timing of the dominant kernel (bench.py)
-            // (only passes over the whole store: bench.py's roofline multiplies the
-            // sampled time by the shard's frames per launch)
-            const bool sample =
-                !view.on && c->samp_every > 0 && (c->samp_count++ % c->samp_every) == 0 &&
-                2 * (size_t)c->samp_used + 1 < c->samp_ev.size();
-            if (sample)
-                c->samp_form[c->samp_used] = form;
-            if (fused) {
-                if (sample)
-                    EK_HIP(hipEventRecord(c->samp_ev[2 * c->samp_used],
-                                          c->stream));
-                ek_launch_round_pass(R, c->stream);
-                if (sample) {
-                    EK_HIP(hipEventRecord(c->samp_ev[2 * c->samp_used + 1],
-                                          c->stream));
-                    c->samp_used++;
-                }
-                ek_launch_round_chain(R, 0, c->stream);
-                ek_launch_round_next(R, 0, c->stream);
-                ek_launch_round_ti(R, goal, c->stream);
-                EK_CHECK_LAUNCH();
-                pending = true;
-                continue;
-            }
-            ek_launch_plan(c->recsT, form, c->A, form, R.cutoff, c->planD,
-                           c->plan, c->hist, c->ctl, c->stream);
-            if (sample)
-                EK_HIP(hipEventRecord(c->samp_ev[2 * c->samp_used], c->stream));
-            ek_launch_pass(form, S.tiles, S.qtiles, S.G, S.dist, S.assign,
-                           c->vecs, S.n, S.n_pad, c->A, c->recsT, c->plan,
-                           c->blockmax, c->ctile, c->ctrace, c->stream);
-            if (sample) {
-                EK_HIP(hipEventRecord(c->samp_ev[2 * c->samp_used + 1],
-                                      c->stream));
-                c->samp_used++;
-            }
-            if (c->chain) {
-                ek_launch_chain_max(S.dist, c->vecs, S.n, S.n_pad, c->plan,
-                                    c->pm, 1, c->goff, c->stream);
-                ek_launch_chain_decide_local(c->blockmax, c->pm, nb,
-                                             ek_chain_max_blocks(S.n), c->goff,
-                                             R.cutoff, c->plan, c->hist,
-                                             c->ctl, c->stream);
-                ek_launch_chain_apply(c->vecs, S.n, S.n_pad, S.dist, S.assign,
-                                      c->plan, c->blockmax, c->stream);
-            } else {
-                for (int j = 1; j < form; ++j) {
-                    ek_launch_localmax_check(c->blockmax, nb, c->goff, R.cutoff,
-                                             c->plan, c->hist, c->ctl, c->stream);
-                    ek_launch_apply(c->vecs, S.G, S.n, S.n_pad, c->A, S.dist,
-                                    S.assign, c->plan, c->blockmax, c->stream);
-                }
-            }
-            ek_launch_pickT(c->blockmax, nb, S.tiles, S.G, S.assign, c->A, form,
-                            c->goff, c->recsT, c->ctl, c->top, c->stream);
-            EK_CHECK_LAUNCH();
-        }
-        EK_HIP(hipEventRecord(c->evb1, c->stream));
-        // ---- the look for the next decision rides on this batch ----------------------
-        if (view_mode && look_pause > 0) {
-            --look_pause;
-        } else if (view_mode) {
-            const int64_t want_cap =
-                forced ? c->n : (int64_t)std::ceil(shrink * (double)c->n);
-            if (ek_view_alloc(c, want_cap) == EK_OK) {
-                EK_HIP(hipMemsetAsync(c->v_count, 0, sizeof(look_cnt), c->stream));
-                ek_launch_view_look(S.dist, S.n, c->ctl, rho, EK_VIEW_REL, EK_VIEW_ABS,
-                                    c->v_count, c->stream);
-                if (view.on)
-                    ek_launch_view_look(c->dist, c->n, c->ctl, rho, EK_VIEW_REL,
-                                        EK_VIEW_ABS, c->v_count + 1, c->stream);
-                EK_CHECK_LAUNCH();
-                EK_HIP(hipMemcpyAsync(look_cnt, c->v_count, sizeof(look_cnt),
-                                      hipMemcpyDeviceToHost, c->stream));
-                looked = true;
-            } else {
-                (void)hipGetLastError();
-                view_mode = 0;  // (no memory for it: the run is what it was without)
-            }
-        }
-        const int32_t before = cr.n_done;
-        EK_HIP(hipMemcpyAsync(&cr, c->ctl, sizeof(cr), hipMemcpyDeviceToHost,
-                              c->stream));
-        unsigned long long ti_now[2] = {ti_seen[0], ti_seen[1]};
-        if (R.tmask)
-            EK_HIP(hipMemcpyAsync(ti_now, c->ti_stats, sizeof(ti_now),
-                                  hipMemcpyDeviceToHost, c->stream));
-        EK_HIP(ek_wait(c));
-        if (R.tmask) {
-            const unsigned long long looked = ti_now[0] - ti_seen[0],
-                                     left = ti_now[1] - ti_seen[1];
-            ti_seen[0] = ti_now[0];
-            ti_seen[1] = ti_now[1];
-            if (looked > 0 && left * 50 < looked) {     // under 2 % left out
-                ti_pause = ti_pause_next;
-                ti_pause_next = std::min(2 * ti_pause_next, 64);
-            } else {
-                ti_pause_next = 2;
-            }
-        } else if (ti_pause > 0 && !one) {
-            --ti_pause;
-        }
-        const int32_t got = cr.n_done - before;
-        // passes that really ran (a step that finds the stop rule met returns at once)
-        const int32_t ran = one ? got : cr.n_rounds - rounds_before;
-        rounds_before = cr.n_rounds;
-        c->st_rounds[ek_form_slot(form)] += ran;
-        c->st_centers[ek_form_slot(form)] += got;
-        c->view_stats[1] += (int64_t)ran * S.n;
-        c->view_stats[2] += (int64_t)ran * (c->n - S.n);
-        if (view.on && cr.stopped) {
-            // The view's maximum is at or below its guard (or the cut-off): the
-            // centers from here on may move settled frames, and the shard's maximum
-            // may be one of them.  Back to the whole store, which decides whether
-            // this is the run's stop; the next look at the policy comes after a batch
-            // has given the shard's own maximum.
-            if ((double)cr.last_max > dist_cutoff)
-                c->view_stats[3]++;
-            leave_view(pending);
-            const int32_t zero = 0;     // (what the stop latched: the flag; the plan's
-            // `go` is made again by the bootstrap, the limit never changed)
-            EK_HIP(hipMemcpyAsync(&c->ctl->stopped, &zero, sizeof(zero),
-                                  hipMemcpyHostToDevice, c->stream));
-            EK_HIP(ek_wait(c));
-            cr.stopped = 0;
-            held = -1;
-            looked = false;     // (it counted in the view's space, against its maximum)
-            if (cr.n_done < goal)
-                continue;
-        }
-        if (cr.stopped || cr.n_done >= goal)
-            break;
-        if (!one)
-            per_round = std::max(1.0, (double)got / std::max(ran, 1));
-        if (cap_adaptive && !one && fused && ran > 0 && !probing) {
-            const double yield = (double)got / ((double)ran * form);
-            if (cap_probing) {
-                cap_probing = false;
-                if (form == cap_form && yield > cap_yield_home + 0.1) {
-                    cap_next_wait = 2;          // the other value is home now
-                } else {
-                    cap = cap == 4 ? 16 : 4;    // back
-                    cap_wait = cap_next_wait;
-                    cap_next_wait = std::min(2 * cap_next_wait, 64);
-                }
-            } else if (cap_wait > 0) {
-                --cap_wait;
-            } else if (yield < 0.65 && left > 4 * form) {
-                cap_yield_home = yield;
-                cap_form = form;
-                cap = cap == 4 ? 16 : 4;
-                cap_probing = true;
-            }
-        }
-        if (!adaptive)
-            continue;
-        // ---- which form next ---------------------------------------------------------
-        float bms = 0.f;
-        EK_HIP(hipEventElapsedTime(&bms, c->evb0, c->evb1));
-        const double rate = got / std::max((double)bms, 1e-6);
-        if (probing) {
-            probing = false;
-            since = 0;
-            if (rate > rate_home) {     // the probed form wins: it is home now
-                for (int q = 0; q < n_ladder; ++q)
-                    if (ladder[q] == form)
-                        home = q;
-                rate_home = rate;
-                gap = 8;
-            } else {                    // back, and wait twice as long
-                form = ladder[home];
-                gap = std::min(gap * 2, 1024);
-            }
-            continue;
-        }
-        rate_home = rate;
-        since += got;
-        if (since >= gap) {
-            // Which neighbour on the ladder is worth a look?  One-center steps
-            // can only win while rounds accept fewer than ~1.4 centers (the cost
-            // ratio of the two forms); a narrower round only while the wider one
-            // accepts fewer than the narrower could at its lower cost (8 / 16:
-            // cost ratio <= 1.35); a wider round only if the chain of the
-            // current one is usually accepted whole -- it breaks where the
-            // farthest point is not a stored candidate, and more candidates
-            // behind that point change nothing.
-            const int T = ladder[home];
-            const bool up_ok = home + 1 < n_ladder &&
-                               (T == 1 || per_round >= 0.8 * T);
-            bool down_ok = home > 0;
-            if (down_ok && ladder[home - 1] == 1)
-                down_ok = per_round < 1.8;
-            else if (down_ok)
-                down_ok = per_round < 1.35 * ladder[home - 1];
-            int target = -1;
-            if (up_ok && down_ok)
-                target = probe_up ? home + 1 : home - 1;
-            else if (up_ok)
-                target = home + 1;
-            else if (down_ok)
-                target = home - 1;
-            if (target >= 0) {
-                probe_up = target > home ? 0 : 1;
-                form = ladder[target];
-                probing = true;
-            } else {
-                since = 0;
-            }
-        }
-    }
-    if (pending) {              // the last round's accepted chain
-        ek_launch_round_flush(R, c->stream);
-        pending = false;
-        EK_CHECK_LAUNCH();
-    }
-    if (view.on || (held < 0 && cr.n_done > first_label)) {
-        // The run ends under a view (or just left one): results back, then the
-        // records and the maximum of the state as the whole store has it -- what the
-        // last round's pick leaves without a view.
-        if (view.on)
-            leave_view(pending);
-        ek_launch_blockmax(S.dist, S.n, c->blockmax, c->stream);
-        if (form == 1) {
-            ek_launch_pick(c->blockmax, nb, S.dist, S.tiles, S.G, S.n, c->A, c->goff,
-                           c->recsT, c->ctl, c->stream);
-        } else {
-            R.T = form;
-            ek_launch_round_chain(R, 1, c->stream);
-            ek_launch_round_next(R, 1, c->stream);
-        }
-        EK_CHECK_LAUNCH();
-        held = form;
-        EK_HIP(hipMemcpyAsync(&cr, c->ctl, sizeof(cr), hipMemcpyDeviceToHost, c->stream));
-        EK_HIP(ek_wait(c));
-    }
-    if (tri) {
-        unsigned long long st[2] = {0, 0};
-        EK_HIP(hipMemcpyAsync(st, c->ti_stats, sizeof(st), hipMemcpyDeviceToHost,
-                              c->stream));
-        EK_HIP(ek_wait(c));
-        c->ti_tiles = (int64_t)st[0];
-        c->ti_skipped = (int64_t)st[1];
-    }
-    EK_HIP(hipEventRecord(c->ev1, c->stream));
-    EK_HIP(ek_wait(c));
-    EK_HIP(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-    // leave the records describing the state: [0] = the shard's farthest point
-    if (held == 1) {
-        ek_launch_blockmax(c->dist, c->n, c->blockmax, c->stream);
-        EK_CHECK_LAUNCH();
-    }
-    if (held >= 0)              // (nothing ran: the slot still describes the state)
-        EK_HIP(hipMemcpyAsync(c->rec, c->recsT, ek_rec_bytes(c->A),
-                              hipMemcpyDeviceToDevice, c->stream));
-    EK_HIP(ek_wait(c));
-    const int32_t added_t = std::min(max_new, std::max(0, cr.n_done - first_label));
-    // (passes over the frames: a round of 32 is two)
-    const int64_t passes = c->st_rounds[0] + c->st_rounds[1] + c->st_rounds[2] +
-                           c->st_rounds[3] + 2 * c->st_rounds[4];
-    c->last_launches = (int32_t)passes;
-    c->last_passes = (int32_t)passes;
-    if (n_added)
-        *n_added = added_t;
-    if (final_maxdist)
-        *final_maxdist = cr.last_max;
-    if (added_t > 0 && (center_index_out || center_dist_out)) {
-        rc = ek_history_download(c, first_label, added_t, center_index_out,
-                                 center_dist_out, nullptr);
-        if (rc)
-            return rc;
-    }
-    return EK_OK;
-}
-
-extern "C" int ek_kcenters_run(ek_ctx *c, int32_t first_label, int32_t max_new,
-                               double dist_cutoff, int32_t *n_added,
-                               int64_t *center_index_out,
-                               float *center_dist_out, float *final_maxdist)
-{
-    if (!c)
-        return ek_fail(EK_EARG, "NULL context");
-    if (!c->loaded)
-        return ek_fail(EK_ESTATE, "ek_kcenters_run: no frames loaded");
-    if (first_label < 0 || max_new < 0)
-        return ek_fail(EK_EARG, "ek_kcenters_run: negative argument");
-    EK_HIP(hipSetDevice(c->device));
-    int rc = ek_ensure_hist(c, first_label + max_new);
-    if (rc)
-        return rc;
-    // the accepted-label counter restarts at first_label for this run
-    EkCtl ctl0;
-    memset(&ctl0, 0, sizeof(ctl0));
-    ctl0.n_done = first_label;
-    EK_HIP(hipMemcpyAsync(c->ctl, &ctl0, offsetof(EkCtl, last_max),
-                          hipMemcpyHostToDevice, c->stream));
-    EK_HIP(ek_wait(c));
-
-    const int T = ek_pick_cands(c, true);
-    // (the triangle inequality's bookkeeping lives in ek_run_rounds, also for one
-    // center per pass)
-    if ((T > 1 || c->tri) && c->n > 0)
-        return ek_run_rounds(c, T, first_label, max_new, dist_cutoff, n_added,
-                             center_index_out, center_dist_out, final_maxdist);
-
-    // With no distance cut-off the trip count is known: enqueue everything.
-    // With a cut-off, enqueue in batches and look at the stop flag in between
-    // (steps enqueued past the stopping point are no-ops on the device).
-    const bool open_loop = !(dist_cutoff > 0.0);
-    const int32_t batch = open_loop ? max_new : 16;
-    int32_t issued = 0;
-    EkCtl ctl;
-    memset(&ctl, 0, sizeof(ctl));
-    ctl.n_done = first_label;
-    EK_HIP(hipEventRecord(c->ev0, c->stream));
-    while (issued < max_new) {
-        const int32_t todo = std::min(batch, max_new - issued);
-        for (int32_t i = 0; i < todo; ++i) {
-            rc = ek_kcenters_step(c, nullptr, 1, first_label + issued + i,
-                                  dist_cutoff, nullptr);
-            if (rc)
-                return rc;
-        }
-        issued += todo;
-        if (!open_loop) {
-            EK_HIP(hipMemcpyAsync(&ctl, c->ctl, sizeof(ctl),
-                                  hipMemcpyDeviceToHost, c->stream));
-            EK_HIP(ek_wait(c));
-            if (ctl.stopped)
-                break;
-        }
-    }
-    EK_HIP(hipEventRecord(c->ev1, c->stream));
-    EK_HIP(hipMemcpyAsync(&ctl, c->ctl, sizeof(ctl), hipMemcpyDeviceToHost,
-                          c->stream));
-    EK_HIP(ek_wait(c));
-    EK_HIP(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-    const int32_t added = std::max(0, ctl.n_done - first_label);
-    c->last_launches = added;
-    if (n_added)
-        *n_added = added;
-    if (final_maxdist)
-        *final_maxdist = ctl.last_max;
-    if (added > 0 && (center_index_out || center_dist_out)) {
-        rc = ek_history_download(c, first_label, added, center_index_out,
-                                 center_dist_out, nullptr);
-        if (rc)
-            return rc;
-    }
-    return EK_OK;
-}
-
-extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
-{
-    if (!c || !out)
-        return ek_fail(EK_EARG, "ek_view_layout_check: NULL argument");
-    if (!c->loaded || c->n <= 0)
-        return ek_fail(EK_ESTATE, "ek_view_layout_check: no frames loaded");
-    EK_HIP(hipSetDevice(c->device));
-    out[0] = out[1] = out[2] = out[3] = 0;
-    int rc = ek_view_alloc(c, c->n);
-    if (rc)
-        return rc;
-    uint32_t nv = 0;
-    ek_launch_view_select(c->dist, c->n, theta, c->v_blockcnt, c->v_blockoff, c->v_act,
-                          c->view_cap, c->v_count, c->stream);
-    EK_CHECK_LAUNCH();
-    EK_HIP(hipMemcpyAsync(&nv, c->v_count, sizeof(nv), hipMemcpyDeviceToHost, c->stream));
-    EK_HIP(ek_wait(c));
-    out[0] = nv;
-    if (nv == 0 || (int64_t)nv > c->view_cap)
-        return EK_OK;
-    const size_t nt = ((size_t)nv + EK_TILE - 1) / EK_TILE, A3 = (size_t)3 * c->A;
-    const size_t tile_words = nt * A3 * EK_TILE;
-    const size_t quad_bytes = ek_quad_tiles_bytes((int64_t)nt, c->A);
-    // the earlier path into scratch: gather -> frame-minor tiles -> quad copy
-    float *r_aos = nullptr, *r_tiles = nullptr, *r_qtiles = nullptr, *r_dist = nullptr;
-    double *r_G = nullptr;
-    int32_t *r_assign = nullptr;
-    unsigned long long *diff = nullptr, got[3] = {0, 0, 0};
-    hipError_t e = hipMalloc((void **)&r_aos, (size_t)nv * A3 * sizeof(float));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&r_tiles, tile_words * sizeof(float));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&r_qtiles, quad_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&r_G, (size_t)nv * sizeof(double));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&r_dist, (size_t)nv * sizeof(float));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&r_assign, (size_t)nv * sizeof(int32_t));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&diff, sizeof(got));
-    if (e == hipSuccess)
-        e = hipMemsetAsync(diff, 0, sizeof(got), c->stream);
-    if (e == hipSuccess)
-        e = ek_view_poison(c);
-    if (e == hipSuccess) {
-        ek_launch_view_gather(c->v_act, nv, c->A, c->aos, c->G, c->dist, c->assign, r_aos,
-                              r_tiles, r_G, r_dist, r_assign, c->stream);
-        ek_launch_quad_tiles(r_tiles, (int64_t)nt, c->A, r_qtiles, c->stream);
-        // a rebuild, and the tiles a reader under the view would ask for
-        if (!ek_view_build(c, nv))
-            ek_launch_view_tiles(c->v_qtiles, (int64_t)nt, c->A, c->v_tiles, c->stream);
-        if (c->qt_valid)
-            ek_launch_view_diff(c->v_qtiles, r_qtiles, quad_bytes / 4, diff, c->stream);
-        ek_launch_view_diff(c->v_tiles, r_tiles, tile_words, diff + 1, c->stream);
-        ek_launch_view_diff(c->v_aos, r_aos, (size_t)nv * A3, diff + 2, c->stream);
-        ek_launch_view_diff(c->v_G, r_G, (size_t)nv * 2, diff + 2, c->stream);
-        ek_launch_view_diff(c->v_dist, r_dist, (size_t)nv, diff + 2, c->stream);
-        ek_launch_view_diff(c->v_assign, r_assign, (size_t)nv, diff + 2, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(got, diff, sizeof(got), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess)
-        e = ek_wait(c);
-    else
-        (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(r_aos);
-    (void)hipFree(r_tiles);
-    (void)hipFree(r_qtiles);
-    (void)hipFree(r_G);
-    (void)hipFree(r_dist);
-    (void)hipFree(r_assign);
-    (void)hipFree(diff);
-    EK_HIP(e);
-    out[1] = (int64_t)got[0];
-    out[2] = (int64_t)got[1];
-    out[3] = (int64_t)got[2];
-    return EK_OK;
-}
-
-extern "C" int ek_view_stats(ek_ctx *c, int64_t *stats)
-{
-    if (!c || !stats)
-        return ek_fail(EK_EARG, "ek_view_stats: NULL argument");
-    for (int k = 0; k < 4; ++k)
-        stats[k] = c->view_stats[k];
-    return EK_OK;
-}
-
 // ---- sampled timing of the distance kernel ---------------------------------------
 extern "C" int ek_timing_begin(ek_ctx *c, int32_t sample_every,
                                int32_t max_samples)

@@ -1,6 +1,7 @@
 // ek_api_ms.hip -- the C ABI of include/enspara_hip.h: multi-candidate rounds across
 // shards (ek_spec_*: three exchanges per round; ek_ms_*: one).
 #include "ek_ctx.h"
+#include "ek_run_policy.h"
 
 // ---- multi-candidate rounds across shards --------------------------------------------
 extern "C" int ek_spec_candidates(ek_ctx *c)
@@ -239,53 +240,9 @@ extern "C" int ek_spec_progress(ek_ctx *c, int32_t *n_done, int32_t *stopped)
 // ---- rounds across shards: one exchange per round (ek_mshard.hip) ------------------------
 // records a shard offers per exchange: EK_MS_SLOTS over all shards, at most the 64 its
 // pick lists (round 6: twice round 5's -- the plan kernel lets the 64 farthest compete)
-// Rounds of 8 between two looks at the ladder.  Rounds 3-5: 24 exchanges, of which the
-// early ones were a third exchanges without a pass -- 17 to 19 passes.  With the headers
-// first (round 6) an exchange is a pass, and 24 of them kept the million-frame fit in
-// rounds of 8 for 74 passes instead of 56 (0.338 s against 0.321); 12: 47 passes, 0.318 s
-// (16: 0.340; the 125 000-frame shard does not care: 12.85 / 13.0 / 12.9 us per center).
-// -DEK_MS_BATCH8=.. builds the others.
-#ifndef EK_MS_BATCH8
-#define EK_MS_BATCH8 12
-#endif
 static int ek_ms_offer(int world)
 {
     return std::max(1, std::min(64, EK_MS_SLOTS / std::max(world, 1)));
-}
-
-static void ek_round_of(ek_ctx *c, int T, double cutoff, EkRound &R)
-{
-    R.dist = c->dist;
-    R.assign = c->assign;
-    R.vecs = c->vecs;
-    R.n = c->n;
-    R.n_pad = c->n_pad;
-    R.goff = c->goff;
-    R.A = c->A;
-    R.T = T;
-    R.tiles = c->tiles;
-    R.qtiles = c->qtiles;
-    R.aos = c->aos;
-    R.G = c->G;
-    R.recs = c->recsT;
-    R.plan = c->plan;
-    R.pend = c->pend;
-    R.ord = c->ord;
-    R.blockmax = c->blockmax;
-    R.pm = c->pm;
-    R.fm = c->fine_pick ? c->fm : nullptr;
-    R.sweep = (c->pass_sweep == 2 ||
-               (c->pass_sweep == 1 && c->n <= (int64_t)2048 * EK_TILE)) ? 1 : 0;
-    R.top = c->top;
-    R.ctile = c->ctile;
-    R.ctrace = c->ctrace;
-    R.hist = c->hist;
-    R.ctl = c->ctl;
-    R.tick = c->tick;
-    R.rows = c->rows;
-    R.vmask = c->vmask;
-    R.cutoff = cutoff;
-    R.pick_cap = c->pick_cap > 0 ? c->pick_cap : 4;
 }
 
 extern "C" int ek_ms_setup(ek_ctx *c, int32_t world, int32_t rank,
@@ -626,33 +583,13 @@ extern "C" int ek_ms_run(ek_ctx *c, int32_t first_label, int32_t max_new,
                        c->ms_peers, c->ms_x.world);
     if (first_label < 0 || max_new < 0)
         return ek_fail(EK_EARG, "ek_ms_run: negative argument");
-    // Rounds of 8 or of 16 candidates: early in a fit every new center reshapes
-    // most frames' distances and a round accepts one to three of its guesses --
-    // eight of them then cost less than sixteen.  ek_run_rounds moves between
-    // the forms by measured centers per ms; here every shard has to take the
-    // SAME decision at the same round, so it is taken from what they all see
-    // alike: the centers the rounds of a batch accepted.  Rounds of 8 while they
-    // accept fewer than 6.5; a batch of 16 that accepts fewer than 8.5 per round
-    // goes back to 8 and the next try waits twice as many batches.  On SMALL shards
-    // (option key 18 = 1, set by sharded.kcenters_sharded for every rank alike when
-    // the largest shard has under 300 000 frames) 4.5 and 5.5: with the exchange's
-    // tails a round of 16 costs only 1.3 x a round of 8 on a 125 000-frame shard and
-    // the ladder lost 7 % there to staying narrow too long -- while at 10^6 frames
-    // per shard the lower thresholds cost 8 % (a third of the early rounds of 16
-    // break and are offered again, 0.2 ms each).  A change of
-    // form costs one exchange without a pass (the state's farthest frames are
-    // offered again).  Results do not depend on the form.
-    // Round 5: rounds of 32 -- two passes of 16 behind ONE plan, chain and
-    // exchange -- once rounds of 16 are usually accepted whole (>= 14 per round);
-    // back to 16 when a batch of them accepts fewer than 22 per round (what 16
-    // would accept at most, with half the passes), the next try twice as far off.
+    // (which form when, and how long a batch: EkGroupLadder, ek_run_policy.h)
     const int Tmax = ek_pick_cands(c, true, true);
     if (Tmax < 4)
         return ek_fail(EK_ESTATE, "ek_ms_run: multi-candidate rounds are off "
                                   "(option key 4 = 1: use ek_kcenters_step)");
-    const bool ladder = Tmax >= 16 && c->cands == -1 && c->adapt;
-    const double up16 = c->ms_small ? 4.5 : 6.5, down16 = c->ms_small ? 5.5 : 8.5;
-    int T = ladder ? 8 : Tmax;
+    EkGroupLadder ladder(Tmax >= 16 && c->cands == -1 && c->adapt, Tmax, c->ms_small != 0);
+    int T = ladder.first();
     rc = ek_ms_begin_T(c, first_label, first_label + max_new, T);
     if (rc)
         return rc;
@@ -670,17 +607,12 @@ extern "C" int ek_ms_run(ek_ctx *c, int32_t first_label, int32_t max_new,
     cr.n_done = first_label;
     EkMsState st;
     memset(&st, 0, sizeof(st));
-    double per_round = 0.6 * T;
+    double per_round = ek_per_round_guess(T);
     int32_t rounds_before = 0, passes = 0;
-    int wait16 = 0, next_wait = 1, wait32 = 0, next_wait32 = 1;
     // (far frames per label on the pick's list, 4 <-> 16 by the yield: as in
     // ek_run_rounds, from numbers every shard sees alike)
-    int cap = c->pick_cap > 0 ? c->pick_cap : 4;
-    const bool cap_adaptive = c->pick_cap <= 0;
-    bool cap_probing = false;
-    int cap_wait = 0, cap_next_wait = 2, cap_form = 0;
-    double cap_yield_home = 0.0;
-    R.pick_cap = cap;
+    EkPickCap cap(c->pick_cap);
+    R.pick_cap = cap.cap;
     for (int k = 0; k < EK_N_FORMS; ++k)
         c->st_rounds[k] = c->st_centers[k] = 0;
     // (the run's own counters: ek_ms_diag)
@@ -693,10 +625,7 @@ extern "C" int ek_ms_run(ek_ctx *c, int32_t first_label, int32_t max_new,
     c->ms_t_n = 0;
     while (max_new > 0) {
         const int32_t left = goal - cr.n_done;
-        int32_t batch = std::max(2, std::min(256, (int32_t)(left / per_round) + 2));
-        if (ladder)
-            batch = std::min(batch, T == 8 ? EK_MS_BATCH8 : (T == 16 ? 64 : 48));
-
+        const int32_t batch = ek_batch_group(T, left, per_round, ladder.on);
         for (int32_t r = 0; r < batch; ++r) {
             rc = ek_ms_enqueue_local(c, R, x, r == 0 ? c->ms_ev : nullptr);
             if (rc)
@@ -725,69 +654,25 @@ extern "C" int ek_ms_run(ek_ctx *c, int32_t first_label, int32_t max_new,
         c->ms_last = st;
         passes += (T == 32 ? 2 : 1) * ran;      // (a round of 32 streams the frames twice)
         c->st_rounds[ek_form_slot(T)] += ran;
-        c->st_centers[ek_form_slot(T)] += cr.n_done - before;
+        const int32_t got = cr.n_done - before;
+        c->st_centers[ek_form_slot(T)] += got;
         if (st.err || st.mode == 0 || cr.stopped || cr.n_done >= goal)
             break;
-        per_round = std::max(1.0, (double)(cr.n_done - before) / std::max(ran, 1));
-        if (cap_adaptive && ran > 0) {
-            const double yield = (double)(cr.n_done - before) / ((double)ran * T);
-            if (cap_probing) {
-                cap_probing = false;
-                if (T == cap_form && yield > cap_yield_home + 0.1) {
-                    cap_next_wait = 2;
-                } else {
-                    cap = cap == 4 ? 16 : 4;
-                    cap_wait = cap_next_wait;
-                    cap_next_wait = std::min(2 * cap_next_wait, 64);
-                }
-            } else if (cap_wait > 0) {
-                --cap_wait;
-            } else if (yield < 0.65 && goal - cr.n_done > 4 * T) {
-                cap_yield_home = yield;
-                cap_form = T;
-                cap = cap == 4 ? 16 : 4;
-                cap_probing = true;
-            }
-            R.pick_cap = cap;
-        }
-        if (ladder && ran > 0) {
-            int want = T;
-            if (T == 8) {
-                if (wait16 > 0)
-                    --wait16;
-                else if (per_round >= up16)
-                    want = 16;
-            } else if (T == 16) {
-                if (per_round < down16) {
-                    want = 8;
-                    wait16 = next_wait;
-                    next_wait = std::min(2 * next_wait, 64);
-                } else {
-                    next_wait = 1;
-                    if (wait32 > 0)
-                        --wait32;
-                    else if (Tmax == 32 && per_round >= 14.0)
-                        want = 32;
-                }
-            } else if (per_round < 22.0) {
-                want = 16;
-                wait32 = next_wait32;
-                next_wait32 = std::min(2 * next_wait32, 64);
-            } else {
-                next_wait32 = 1;
-            }
-            if (want != T) {
-                ek_launch_round_flush(R, c->stream);    // the chain still pending
-                EK_CHECK_LAUNCH();
-                rc = ek_ms_begin_T(c, cr.n_done, goal, want);
-                if (rc)
-                    return rc;
-                T = want;
-                ek_round_of(c, T, dist_cutoff, R);
-                R.pick_cap = cap;
-                rounds_before = 0;
-                per_round = std::max(per_round, 0.6 * T);
-            }
+        per_round = std::max(1.0, (double)got / std::max(ran, 1));
+        cap.update(T, got, ran, goal - cr.n_done);
+        R.pick_cap = cap.cap;
+        const int want = ladder.update(T, per_round, ran);
+        if (want != T) {
+            ek_launch_round_flush(R, c->stream);    // the chain still pending
+            EK_CHECK_LAUNCH();
+            rc = ek_ms_begin_T(c, cr.n_done, goal, want);
+            if (rc)
+                return rc;
+            T = want;
+            ek_round_of(c, T, dist_cutoff, R);
+            R.pick_cap = cap.cap;
+            rounds_before = 0;
+            per_round = std::max(per_round, ek_per_round_guess(T));
         }
     }
     EK_HIP(hipEventRecord(c->ev1, c->stream));

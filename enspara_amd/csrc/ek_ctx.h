@@ -1,6 +1,7 @@
 // ek_ctx.h -- the context behind the C ABI and what the files that implement it
-// share (ek_api.hip: context, loading, state, k-centers; ek_api_pam.hip: the PAM
-// entry points; ek_api_ms.hip: rounds across shards).  Host side only.
+// share (ek_api.hip: context, loading, state, k-centers steps; ek_api_run.hip: the
+// k-centers run loop and the active view; ek_api_pam.hip: the PAM entry points;
+// ek_api_ms.hip: rounds across shards).  Host side only.
 #pragma once
 #include "ek_common.h"
 #include "ek_pam_sparse.h"
@@ -381,5 +382,9 @@ int ek_ensure_hist(ek_ctx *c, int32_t label);
 void ek_pam_forget(ek_ctx *c);
 int ek_upload_centers(ek_ctx *c, const float *xyz, int32_t K);
 int ek_free_all(ek_ctx *c);
+hipError_t ek_malloc_named(ek_ctx *c, void **ptr, size_t bytes, const char *name);
+// helpers defined in ek_api_run.hip
 void ek_view_free(ek_ctx *c);     // the active view's buffers (ek_run_rounds)
+// the descriptor of a round of T candidates over the shard's own store
+void ek_round_of(ek_ctx *c, int T, double cutoff, EkRound &R);
 

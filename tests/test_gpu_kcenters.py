@@ -430,3 +430,31 @@ def test_per_prefix_maxima_in_the_pass_or_in_the_chain_kernel(ocl, sweep, n, A, 
     assert list(r.center_indices) == [int(i) for i in inds]
     np.testing.assert_array_equal(r.assignments, a)
     np.testing.assert_array_equal(r.distances, d)
+
+
+@pytest.mark.parametrize("view", [1, 2])
+@pytest.mark.parametrize("cands", [16, 8])
+def test_pinned_form_decides_by_counts_alone(cands, view):
+    """With the form pinned no decision of the run loop (csrc/ek_run_policy.h: pick
+    cap, active view and its pauses, batch lengths) rests on a measured time: two
+    fits of one store take the same rounds, build the same views and give the same
+    result."""
+    from test_gpu_active_view import _clouds
+    x = _clouds(40, 61, 20, seed=20)
+    assert len(x) == 2440
+    runs = []
+    with _store(x) as st:
+        st.set_option("candidates", cands)
+        st.set_option("active_view", view)
+        for _ in range(2):
+            st.reset_state()
+            idx, cd, fmax = st.kcenters_run(0, 60, 0.0)
+            d, a = st.download_state()
+            runs.append((st.run_stats(), st.view_stats(), idx, cd, fmax, d, a))
+    (rs0, vs0, *r0), (rs1, vs1, *r1) = runs
+    assert rs0 == rs1 and vs0 == vs1
+    assert len(r0[0]) == 60 and sum(k for _, k in rs0.values()) == 60
+    for u, v in zip(r0, r1):
+        np.testing.assert_array_equal(u, v)
+    if view == 2:
+        assert vs0["views"] > 0 and vs0["left_out"] > 0

@@ -56,6 +56,9 @@ SYMBOLS = [
     "ek_cards_last_timing", "ek_cards_close", "ek_cards_scan_chunk",
     "ek_sasa_open", "ek_sasa_run", "ek_sasa_last_timing", "ek_sasa_close",
     "ek_wmi_run", "ek_wmi_last_timing",
+    "ek_pockets_open", "ek_pockets_run", "ek_pockets_counts", "ek_pockets_fetch",
+    "ek_pockets_last_timing", "ek_pockets_close", "ek_pockets_touches", "ek_pockets_ranks",
+    "ek_pockets_labels",
     "ek_rotamer_states", "ek_dihedral_angles", "ek_dihedral_rotamers",
     "ek_krylov_create", "ek_krylov_destroy", "ek_krylov_set_vector",
     "ek_krylov_get_vector", "ek_krylov_step", "ek_krylov_rotate",
@@ -265,6 +268,15 @@ def load():
     L.ek_sasa_close.argtypes = [vp]
     L.ek_wmi_run.argtypes = [C.c_int, u8p, f64p, i64, i32, i32, f64p, f64p]
     L.ek_wmi_last_timing.argtypes = [f64p]
+    L.ek_pockets_open.argtypes = [C.c_int, i32, f64p, C.c_double, i32, C.POINTER(vp)]
+    L.ek_pockets_run.argtypes = [vp, f32p, i64, f32p, i32p, i64]
+    L.ek_pockets_counts.argtypes = [vp, i64, i64p]
+    L.ek_pockets_fetch.argtypes = [vp, i32p, i32p]
+    L.ek_pockets_last_timing.argtypes = [vp, f64p]
+    L.ek_pockets_close.argtypes = [vp]
+    L.ek_pockets_touches.argtypes = [C.c_int, f32p, i32, f64p, C.c_double, f32p, i32p, u8p]
+    L.ek_pockets_ranks.argtypes = [C.c_int, u8p, i32p, u8p]
+    L.ek_pockets_labels.argtypes = [C.c_int, u8p, i32p, i32p]
     L.ek_rotamer_states.argtypes = [C.c_int, f32p, i64, i32, u8p, i32, i32p, f64p, f32p,
                                     C.c_double, u8p, f64p]
     L.ek_dihedral_angles.argtypes = [C.c_int, f32p, i64, i32, i32p, i32, f32p, f64p]

@@ -1,8 +1,11 @@
 """Geometry helpers on the hot path: point-vs-set distances in feature space
 (reference enspara/geometry/libdist.pyx), dihedral angles and buffered rotamer
 states (reference enspara/geometry/rotamer.py), Shrake-Rupley solvent-accessible
-surface areas (``sasa``; what the reference takes from mdtraj)."""
+surface areas (``sasa``; what the reference takes from mdtraj), LIGSITE pocket
+detection (``pockets``; reference enspara/geometry/pockets.py)."""
 from . import libdist  # noqa: F401
 from . import rotamer  # noqa: F401
 from . import sasa  # noqa: F401
+from . import pockets  # noqa: F401
 from .rotamer import all_rotamers  # noqa: F401
+from .pockets import get_pockets, get_pocket_cells, cluster_pocket_cells  # noqa: F401

@@ -716,6 +716,54 @@ int ek_sasa_run(ek_sasa *h, const float *xyz, int64_t frames, int64_t chunk_fram
 int ek_sasa_last_timing(ek_sasa *h, double *ms_out);
 int ek_sasa_close(ek_sasa *h);
 
+/* ---- LIGSITE pocket detection ---------------------------------------------------------
+ * Replaces enspara/geometry/pockets.py (csrc/ek_pockets.hip; the contract is DESIGN.md
+ * 4i).  A handle holds, on the device, cutoff [atoms] float64 = probe + radius in nm (> 0
+ * and finite), the grid spacing (> 0 and finite) and min_rank.  All arrays are host memory.
+ * ek_pockets_run: xyz [frames][atoms][3] float32 in nm, finite; origin [frames][3] float32
+ * = each frame's smallest coordinates and dims [frames][3] = its grid (the caller takes
+ * both from the coordinates), 0 <= dims <= 2048 per axis and at most 2^26 cells a frame
+ * (EK_EARG), so that a flat index (ix * ny + iy) * nz + iz fits int32.  Cell i of an axis
+ * lies at double(origin) + double(i) * spacing, not fused, and touches iff for some atom
+ * (dx*dx + dy*dy) + dz*dz < cutoff * cutoff in float64, d = cell - double(x).  Along each
+ * of the directions (1,0,0), (0,1,0), (0,0,1), (1,1,1), (-1,1,1), (-1,-1,1), (1,-1,1) a cell
+ * that does not touch and lies strictly between its line's first and last touching cell
+ * gains one rank; a diagonal line (sx, sy, 1) whose first cell has x and y on their start
+ * faces (0 if s > 0, else n - 1) and z >= 1 is not scanned (the reference's enumeration
+ * misses those lines).  Pocket cells are the ones with rank >= min_rank; a pocket is a
+ * component of them under 18-connectivity (face and edge neighbours), labelled by its
+ * smallest flat index.  A frame with a zero among its dims has no cells.
+ * chunk_frames > 0: frames of one upload (at most 32768; EK_ENOMEM if they do not fit, and
+ * EK_EARG if they hold 2^30 cells or more); 0: what fits half of the free device memory.
+ * The number of launches of a chunk does not depend on its frames.
+ * ek_pockets_counts: counts_out [frames] = the pocket cells of each frame of the last run
+ * (frames must be that run's).  ek_pockets_fetch: cells_out, labels_out [sum of counts] =
+ * the flat index and the label of every pocket cell, frame after frame, within a frame in
+ * ascending flat index.  ek_pockets_last_timing: ms_out[4] = the last run's uploads, touch
+ * kernels, line-extent and rank kernels, label and compaction kernels, summed over its
+ * chunks, between HIP events.
+ * One dense grid (dims [3], 1 <= cells <= 2^26), each stage alone: ek_pockets_touches:
+ * xyz [atoms][3], cutoff [atoms], origin [3] -> touches_out [cells] bytes 0 / 1;
+ * ek_pockets_ranks: touches [cells] (any non-zero byte touches) -> ranks_out [cells];
+ * ek_pockets_labels: mask [cells] (non-zero = pocket cell) -> labels_out [cells], -1
+ * outside the mask. */
+typedef struct ek_pockets ek_pockets;
+int ek_pockets_open(int device, int32_t atoms, const double *cutoff, double spacing,
+                    int32_t min_rank, ek_pockets **out);
+int ek_pockets_run(ek_pockets *h, const float *xyz, int64_t frames, const float *origin,
+                   const int32_t *dims, int64_t chunk_frames);
+int ek_pockets_counts(ek_pockets *h, int64_t frames, int64_t *counts_out);
+int ek_pockets_fetch(ek_pockets *h, int32_t *cells_out, int32_t *labels_out);
+int ek_pockets_last_timing(ek_pockets *h, double *ms_out);
+int ek_pockets_close(ek_pockets *h);
+int ek_pockets_touches(int device, const float *xyz, int32_t atoms, const double *cutoff,
+                       double spacing, const float *origin, const int32_t *dims,
+                       uint8_t *touches_out);
+int ek_pockets_ranks(int device, const uint8_t *touches, const int32_t *dims,
+                     uint8_t *ranks_out);
+int ek_pockets_labels(int device, const uint8_t *mask, const int32_t *dims,
+                      int32_t *labels_out);
+
 /* ---- joint probabilities and mutual information of weighted frames --------------------
  * Replaces the arithmetic of weighted_mi (enspara/info_theory/mutual_info.py:78-178;
  * csrc/ek_wmi.hip).  codes [frames][F] state codes as bytes (the caller validates them:

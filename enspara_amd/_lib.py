@@ -56,6 +56,10 @@ SYMBOLS = [
     "ek_cards_last_timing", "ek_cards_close", "ek_cards_scan_chunk",
     "ek_sasa_open", "ek_sasa_run", "ek_sasa_last_timing", "ek_sasa_close",
     "ek_wmi_run", "ek_wmi_last_timing",
+    "ek_ent_kl_rows", "ek_ent_js_rows", "ek_ent_shannon_rows", "ek_ent_kl_counts",
+    "ek_ent_last_timing", "ek_ent_state_counts_open", "ek_ent_state_counts_add",
+    "ek_ent_state_counts_read", "ek_ent_state_counts_last_timing",
+    "ek_ent_state_counts_close",
     "ek_pockets_open", "ek_pockets_run", "ek_pockets_counts", "ek_pockets_fetch",
     "ek_pockets_last_timing", "ek_pockets_close", "ek_pockets_touches", "ek_pockets_ranks",
     "ek_pockets_labels",
@@ -268,6 +272,17 @@ def load():
     L.ek_sasa_close.argtypes = [vp]
     L.ek_wmi_run.argtypes = [C.c_int, u8p, f64p, i64, i32, i32, f64p, f64p]
     L.ek_wmi_last_timing.argtypes = [f64p]
+    L.ek_ent_kl_rows.argtypes = [C.c_int, i64, i64, f64p, f64p, f64p, u32p]
+    L.ek_ent_js_rows.argtypes = [C.c_int, i64, i64, f64p, f64p, f64p, f64p, u32p]
+    L.ek_ent_shannon_rows.argtypes = [C.c_int, i64, i64, f64p, i32, f64p]
+    L.ek_ent_kl_counts.argtypes = [C.c_int, i32, f64p, i64, i32p, i32p, i64p, C.c_double,
+                                   f64p, u32p]
+    L.ek_ent_last_timing.argtypes = [f64p]
+    L.ek_ent_state_counts_open.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+    L.ek_ent_state_counts_add.argtypes = [vp, u8p, i64]
+    L.ek_ent_state_counts_read.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.ek_ent_state_counts_last_timing.argtypes = [vp, f64p]
+    L.ek_ent_state_counts_close.argtypes = [vp]
     L.ek_pockets_open.argtypes = [C.c_int, i32, f64p, C.c_double, i32, C.POINTER(vp)]
     L.ek_pockets_run.argtypes = [vp, f32p, i64, f32p, i32p, i64]
     L.ek_pockets_counts.argtypes = [vp, i64, i64p]

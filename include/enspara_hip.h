@@ -782,6 +782,58 @@ int ek_wmi_run(int device, const uint8_t *codes, const double *weights, int64_t 
                int32_t F, int32_t S, double *P_out, double *mi_out);
 int ek_wmi_last_timing(double *ms_out);
 
+/* ---- relative entropy, Shannon entropy, state counts ---------------------------------
+ * Replaces the arithmetic of enspara/info_theory/entropy.py and of compute_rotamer_counts
+ * in enspara/apps/compute-shannon-entropy.py (csrc/ek_entropy.hip).  All arrays are host
+ * memory, all arithmetic is float64, nothing is fused; rows, cols >= 1.
+ * ek_ent_kl_rows: P, Q [rows][cols] -> out[r] = the sum over j of t = P * log(P / Q), in
+ * nats.  A t that is NaN counts as 0 (P = 0 whatever Q is); P > 0 with Q = 0 gives +inf.
+ * flags_out: one word, bit 0 set if some element of P is negative, bit 1 for Q (the
+ * sums are then meaningless; the caller raises).  The terms of a row are added in an
+ * order that its width and the parity of its first flat index fix (csrc/ek_entropy.hip
+ * spells it out): the same bits on every run, no float atomics, not numpy's pairwise
+ * order.  Rows up to 8 wide take one lane each, up to 128 wide 8 lanes, wider a wave.
+ * ek_ent_js_rows: the same walk with m = 0.5 * (P + Q) formed in registers; out_p[r] =
+ * the sum of P * log(P / m), out_q[r] = the sum of Q * log(Q / m).
+ * ek_ent_shannon_rows: out[r] = -(the sum over j of x * log(x)), elements x <= 0 (and NaN)
+ * contribute 0; normalize != 0: x = p / (the row's sum), the sum taken first in the
+ * same order.
+ * ek_ent_kl_counts: Q is built on the device and never leaves it: the n x n matrix of
+ * (double)count + prior from the nnz sparse counts (ci, cj in [0, n), cv >= 0, prior >= 0;
+ * EK_EARG otherwise; every cell at most once, which the caller guarantees and the call
+ * does not check: of a cell given twice one entry is kept, which one is not defined), each row divided as
+ * ek_msm_row_normalize divides it (the row sum added in column order, inv = 1 / sum, 0
+ * for an empty row, Q = inv * Q), then ek_ent_kl_rows' kernel on P [n][n] and Q ->
+ * out [n].
+ * ek_ent_last_timing: ms_out[3] = the last of these calls' upload, building of Q (0
+ * unless ek_ent_kl_counts), row kernel, between HIP events.
+ * EK_ENOMEM if the inputs do not fit the device. */
+int ek_ent_kl_rows(int device, int64_t rows, int64_t cols, const double *P, const double *Q,
+                   double *out, uint32_t *flags_out);
+int ek_ent_js_rows(int device, int64_t rows, int64_t cols, const double *P, const double *Q,
+                   double *out_p, double *out_q, uint32_t *flags_out);
+int ek_ent_shannon_rows(int device, int64_t rows, int64_t cols, const double *p,
+                        int32_t normalize, double *out);
+int ek_ent_kl_counts(int device, int32_t n, const double *P, int64_t nnz, const int32_t *ci,
+                     const int32_t *cj, const int64_t *cv, double prior, double *out,
+                     uint32_t *flags_out);
+int ek_ent_last_timing(double *ms_out);
+/* A handle owns counts [f][n_states] uint64 on the device, zero when opened; f and
+ * n_states within ek_mi_open's limits.  ek_ent_state_counts_add: codes [frames][f] state
+ * codes as bytes (ek_mi_add's layout), 0 <= frames < 2^31 - 64; counts[j][u] += the
+ * number of frames with codes[t][j] == u.  A code >= n_states counts nowhere; the caller
+ * validates.  Lanes run along the feature axis; n_states <= 4 are counted in registers,
+ * more in the LDS; integer atomics only, so the counts do not depend on how the frames are
+ * split.  ek_ent_state_counts_read downloads them.  ek_ent_state_counts_last_timing:
+ * ms_out[2] = the last add's upload, its kernel. */
+typedef struct ek_ent_state_counts ek_ent_state_counts;
+int ek_ent_state_counts_open(int device, int32_t f, int32_t n_states,
+                             ek_ent_state_counts **out);
+int ek_ent_state_counts_add(ek_ent_state_counts *h, const uint8_t *codes, int64_t frames);
+int ek_ent_state_counts_read(ek_ent_state_counts *h, uint64_t *counts_out);
+int ek_ent_state_counts_last_timing(ek_ent_state_counts *h, double *ms_out);
+int ek_ent_state_counts_close(ek_ent_state_counts *h);
+
 /* ---- dihedral angles and buffered rotamer states ------------------------------------
  * Replaces enspara/geometry/rotamer.py (csrc/ek_rotamer.hip).  All arrays are host
  * memory.  A dihedral is of one of n_kinds kinds (kind [n] bytes); kind k has

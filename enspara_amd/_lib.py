@@ -60,6 +60,8 @@ SYMBOLS = [
     "ek_ent_last_timing", "ek_ent_state_counts_open", "ek_ent_state_counts_add",
     "ek_ent_state_counts_read", "ek_ent_state_counts_last_timing",
     "ek_ent_state_counts_close",
+    "ek_kmc_create", "ek_kmc_destroy", "ek_kmc_next", "ek_kmc_trajectories",
+    "ek_kmc_ensemble", "ek_kmc_fret_probs", "ek_kmc_fret_bursts", "ek_kmc_last_timing",
     "ek_pockets_open", "ek_pockets_run", "ek_pockets_counts", "ek_pockets_fetch",
     "ek_pockets_last_timing", "ek_pockets_close", "ek_pockets_touches", "ek_pockets_ranks",
     "ek_pockets_labels",
@@ -283,6 +285,18 @@ def load():
     L.ek_ent_state_counts_read.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.ek_ent_state_counts_last_timing.argtypes = [vp, f64p]
     L.ek_ent_state_counts_close.argtypes = [vp]
+    u64 = C.c_uint64
+    L.ek_kmc_create.argtypes = [C.c_int, i32, i64p, i32p, f64p, C.POINTER(vp)]
+    L.ek_kmc_destroy.argtypes = [vp]
+    L.ek_kmc_next.argtypes = [vp, i64, i32p, f64p, i32p, i64p]
+    L.ek_kmc_trajectories.argtypes = [vp, u64, i64, i64, i32p, i64, i32, i64, i32p, i64p]
+    L.ek_kmc_ensemble.argtypes = [C.c_int, i32, f64p, i64p, i32p, f64p, f64p, i64, f64p,
+                                  f64p, f64p]
+    L.ek_kmc_fret_probs.argtypes = [C.c_int, u64, i64, i64, i32p, i32, i64p, f64p, f64p,
+                                    C.c_double, C.c_double, f64p]
+    L.ek_kmc_fret_bursts.argtypes = [vp, u64, i64, i64, i64p, i64p, f64p, i64p, f64p, f64p,
+                                     C.c_double, C.c_double, i64, u8p, i32p, i64p]
+    L.ek_kmc_last_timing.argtypes = [f64p]
     L.ek_pockets_open.argtypes = [C.c_int, i32, f64p, C.c_double, i32, C.POINTER(vp)]
     L.ek_pockets_run.argtypes = [vp, f32p, i64, f32p, i32p, i64]
     L.ek_pockets_counts.argtypes = [vp, i64, i64p]

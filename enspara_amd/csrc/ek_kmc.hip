@@ -1,0 +1,1027 @@
+// ek_kmc.hip -- kinetic Monte Carlo on a transition matrix, smFRET burst sampling and the
+// propagation of an ensemble.
+//
+// Replaces enspara/msm/synthetic_data.py (synthetic_trajectory :15-46, synthetic_ensemble
+// :49-103) and the burst sampling of enspara/geometry/dyes_from_expt_dist.py
+// (sample_FE_probs :546-559, _sample_FRET_histograms :562-604).  DESIGN.md 4k is the
+// contract; in short:
+//
+// Uniforms.  Philox4x32-10, key = the 64-bit seed (low word first), counter = {i lo, i hi,
+//   chain lo, stream << 28 | chain hi} with i = index >> 1.  The call's words a, b, c, d
+//   give the doubles ((a >> 5) * 2^26 + (b >> 6)) * 2^-53 (index even) and the same of
+//   c, d (index odd), both in [0, 1).  Streams: KMC_TRANS (index = the step left), KMC_INIT
+//   (index 0), KMC_BIN, KMC_JITTER, KMC_COIN (index = the photon within its burst).
+// A step.  The rows of T live compressed (indptr, cols, cdf = cumsum(nonzeros) / last, built
+//   by the host).  The next state is the column of the first cdf entry > u: numpy's
+//   Generator.choice(n, 1, p=row) fed the same double.
+//   lane form   a lane per chain, binary search (kmc_upper); 16 steps are gathered in an
+//               LDS tile per wave and written as 64-byte runs per chain (kmc_tile_flush)
+//   wave form   a wave per chain: while the row is longer than 64 the lanes probe 64
+//               evenly spaced pivots and a ballot picks the stretch (rows up to 4096
+//               nonzeros: one such round), then one load per lane and a ballot.  Lane l
+//               draws the double of step base + l; the states of 64 steps leave in one
+//               256-byte store.
+//   Both search the same cdf for the same first entry > u, so the states are the same.
+//   A launch covers at most `step_cap` steps; (state, step index) is all that is carried.
+// Ensemble.  p <- p T in a fixed order: dense, column j adds p[i] * T[i][j] over blocks of
+//   KMC_ENS_ROWS rows in row order (lanes along the columns), then the blocks' partial sums
+//   in block order; column-compressed, column j adds vals[k] * p[rows[k]] in storage
+//   order.  p . observable: 256 partial sums over k = tid, tid + 256, .., then a tree
+//   in the LDS.  No float atomics anywhere.
+// Bursts.  A lane per burst: the chain starts at the inverse CDF of the populations, runs
+//   to the burst's last frame and serves its photons on the way: bin by inverse CDF of the
+//   state's histogram, d = centre + (u * bin_width - bin_width / 2), d2 = d * d, d6 = d2 *
+//   d2 * d2, E = r06 / (r06 + d6), acceptor iff coin <= E.  One byte per photon.
+// A chain that has to step from a row without nonzeros records the state (integer
+// atomicMin) and stays; the caller raises.
+#include "ek_common.h"
+#include "ek_mi_launch.h"
+
+#include <new>
+
+extern int ek_set_error(int code, const char *fmt, ...);
+
+#define KMC_HIP(call)                                                               \
+    do {                                                                            \
+        hipError_t e_ = (call);                                                     \
+        if (e_ != hipSuccess)                                                       \
+            return ek_set_error(EK_EHIP, "%s failed: %s at %s:%d", #call,           \
+                                hipGetErrorString(e_), __FILE__, __LINE__);         \
+    } while (0)
+
+#define KMC_TRANS 0u
+#define KMC_INIT 1u
+#define KMC_BIN 2u
+#define KMC_JITTER 3u
+#define KMC_COIN 4u
+
+#define KMC_LANE_WG 64          // lane form, bursts: one wave a workgroup (one LDS tile)
+#define KMC_TS 16               // steps of a tile: 64-byte runs per chain
+#define KMC_WAVE_WG 256         // wave form: four chains a workgroup
+#define KMC_WG 256
+#define KMC_STEP_CAP 16384      // steps of a launch unless the caller says otherwise
+#define KMC_BUF_BYTES ((int64_t)256 << 20)  // the trajectories' device buffer
+#define KMC_MIN_CHUNK 1024      // steps of a buffer at least, before the chains are split
+#define KMC_WAVE_MAX_CHAINS 2048    // form 0: up to this many chains take a wave each
+#define KMC_ENS_ROWS 64
+#define KMC_NO_BAD 0xffffffffu
+
+static double kmc_ms[3];        // upload, kernels, download of the last call
+
+struct KmcRows {
+    const int64_t *indptr;
+    const int32_t *cols;
+    const double *cdf;
+    int32_t n;
+};
+
+struct KmcDist {
+    const int64_t *off;         // [n_states + 1]
+    const double *centres, *cdf;
+};
+
+// ---- uniforms ----------------------------------------------------------------------------
+__device__ __forceinline__ void kmc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                           uint32_t k0, uint32_t k1, uint32_t w[4])
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = c0;
+    w[1] = c1;
+    w[2] = c2;
+    w[3] = c3;
+}
+
+__device__ __forceinline__ double kmc_double(uint32_t a, uint32_t b)
+{
+    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+// the two doubles of call i of (stream, chain): indices 2 i and 2 i + 1
+__device__ __forceinline__ void kmc_pair(uint64_t seed, uint32_t stream, uint64_t chain,
+                                         uint64_t i, double &u0, double &u1)
+{
+    uint32_t w[4];
+    kmc_philox((uint32_t)i, (uint32_t)(i >> 32), (uint32_t)chain,
+               (stream << 28) | (uint32_t)(chain >> 32), (uint32_t)seed, (uint32_t)(seed >> 32),
+               w);
+    u0 = kmc_double(w[0], w[1]);
+    u1 = kmc_double(w[2], w[3]);
+}
+
+__device__ __forceinline__ double kmc_uniform(uint64_t seed, uint32_t stream, uint64_t chain,
+                                              uint64_t index)
+{
+    double u0, u1;
+    kmc_pair(seed, stream, chain, index >> 1, u0, u1);
+    return (index & 1) ? u1 : u0;
+}
+
+// ---- the search ----------------------------------------------------------------------------
+// the first k of [lo, hi) with cdf[k] > u; hi - 1 if there is none (hi > lo)
+__device__ __forceinline__ int64_t kmc_upper(const double *__restrict__ cdf, int64_t lo,
+                                             int64_t hi, double u)
+{
+    int64_t a = lo, b = hi - 1;
+    while (a < b) {
+        const int64_t m = (a + b) >> 1;
+        if (cdf[m] > u)
+            b = m;
+        else
+            a = m + 1;
+    }
+    return a;
+}
+
+__device__ __forceinline__ int32_t kmc_step_lane(const KmcRows &R, int32_t s, double u,
+                                                 uint32_t *bad)
+{
+    const int64_t lo = R.indptr[s], hi = R.indptr[s + 1];
+    if (hi <= lo) {
+        atomicMin(bad, (uint32_t)s);
+        return s;
+    }
+    return R.cols[kmc_upper(R.cdf, lo, hi, u)];
+}
+
+// s and u are the same in every lane of the wave
+__device__ __forceinline__ int32_t kmc_step_wave(const KmcRows &R, int32_t s, double u, int lane,
+                                                 uint32_t *bad)
+{
+    int64_t lo = R.indptr[s];
+    int64_t len = R.indptr[s + 1] - lo;
+    if (len <= 0) {
+        if (lane == 0)
+            atomicMin(bad, (uint32_t)s);
+        return s;
+    }
+    while (len > EK_WAVE) {
+        const int64_t stride = (len + EK_WAVE - 1) / EK_WAVE;
+        const int64_t e = (int64_t)(lane + 1) * stride;
+        const int64_t p = lo + (e < len ? e : len) - 1;
+        const unsigned long long mask = __ballot(R.cdf[p] > u);
+        // (no pivot > u cannot be for u < 1, the last cdf being 1.0: then the last stretch)
+        const int64_t j = mask ? (int64_t)(__ffsll(mask) - 1) : (len - 1) / stride;
+        const int64_t b = j * stride, e1 = (j + 1) * stride;
+        len = (e1 < len ? e1 : len) - b;     // (lane j is the first whose pivot is > u: b < len)
+        lo += b;
+    }
+    const bool pred = lane < len && R.cdf[lo + (lane < len ? lane : 0)] > u;
+    const unsigned long long mask = __ballot(pred);
+    const int64_t k = mask ? (int64_t)(__ffsll(mask) - 1) : len - 1;
+    return R.cols[lo + k];
+}
+
+// tile [64 chains][KMC_TS steps] of one wave -> out: chain c's cnt steps go to out[off ..],
+// four chains (64 bytes each) per store instruction.  off, cnt: this lane's chain's.
+__device__ __forceinline__ void kmc_tile_flush(const int32_t (*tile)[KMC_TS + 1], int lane,
+                                               long long off, int cnt, int32_t *__restrict__ out)
+{
+#pragma unroll 4
+    for (int i = 0; i < EK_WAVE / 4; ++i) {
+        const int c = i * 4 + (lane >> 4), j = lane & (KMC_TS - 1);
+        const long long offc = __shfl(off, c, EK_WAVE);
+        const int cntc = __shfl(cnt, c, EK_WAVE);
+        if (j < cntc)
+            out[offc + j] = tile[c][j];
+    }
+}
+
+// ---- chains --------------------------------------------------------------------------------
+// draws t0 .. t0 + m - 1 of every chain: state after draw t0 + j -> out[c * ld + col0 + j]
+__global__ void __launch_bounds__(KMC_LANE_WG)
+kmc_lane_kernel(KmcRows R, uint64_t seed, int64_t first_chain, int64_t n_chains,
+                int32_t *__restrict__ cur, int64_t t0, int64_t m, int32_t *__restrict__ out,
+                int64_t ld, int64_t col0, uint32_t *__restrict__ bad)
+{
+    __shared__ int32_t tile[EK_WAVE][KMC_TS + 1];
+    const int lane = threadIdx.x;
+    const int64_t c = (int64_t)blockIdx.x * KMC_LANE_WG + lane;
+    const bool live = c < n_chains;
+    const uint64_t chain = (uint64_t)(first_chain + c);
+    int32_t s = live ? cur[c] : 0;
+    double u0 = 0.0, u1 = 0.0;
+    for (int64_t j0 = 0; j0 < m; j0 += KMC_TS) {        // (m is the same in every lane)
+        const int cnt = (int)(m - j0 < KMC_TS ? m - j0 : KMC_TS);
+        if (live) {
+            for (int j = 0; j < cnt; ++j) {
+                const uint64_t idx = (uint64_t)(t0 + j0 + j);
+                if (!(idx & 1) || (j0 == 0 && j == 0))
+                    kmc_pair(seed, KMC_TRANS, chain, idx >> 1, u0, u1);
+                s = kmc_step_lane(R, s, (idx & 1) ? u1 : u0, bad);
+                tile[lane][j] = s;
+            }
+        }
+        __syncthreads();
+        kmc_tile_flush(tile, lane, (long long)(c * ld + col0 + j0), live ? cnt : 0, out);
+        __syncthreads();
+    }
+    if (live)
+        cur[c] = s;
+}
+
+__global__ void __launch_bounds__(KMC_WAVE_WG)
+kmc_wave_kernel(KmcRows R, uint64_t seed, int64_t first_chain, int64_t n_chains,
+                int32_t *__restrict__ cur, int64_t t0, int64_t m, int32_t *__restrict__ out,
+                int64_t ld, int64_t col0, uint32_t *__restrict__ bad)
+{
+    const int lane = threadIdx.x & (EK_WAVE - 1);
+    const int64_t c = (int64_t)blockIdx.x * (KMC_WAVE_WG / EK_WAVE) + threadIdx.x / EK_WAVE;
+    if (c >= n_chains)          // (whole waves leave; no barrier below)
+        return;
+    const uint64_t chain = (uint64_t)(first_chain + c);
+    int32_t s = cur[c];
+    for (int64_t j0 = 0; j0 < m; j0 += EK_WAVE) {
+        const int cnt = (int)(m - j0 < EK_WAVE ? m - j0 : EK_WAVE);
+        const double mine = kmc_uniform(seed, KMC_TRANS, chain, (uint64_t)(t0 + j0 + lane));
+        int32_t keep = 0;
+        for (int j = 0; j < cnt; ++j) {
+            const double u = __shfl(mine, j, EK_WAVE);
+            s = __builtin_amdgcn_readfirstlane(kmc_step_wave(R, s, u, lane, bad));
+            if (lane == j)
+                keep = s;
+        }
+        if (lane < cnt)
+            out[c * ld + col0 + j0 + lane] = keep;
+    }
+    if (lane == 0)
+        cur[c] = s;
+}
+
+__global__ void __launch_bounds__(KMC_WG)
+kmc_next_kernel(KmcRows R, int64_t n, const int32_t *__restrict__ states,
+                const double *__restrict__ u, int32_t *__restrict__ next, uint32_t *__restrict__ bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * KMC_WG + threadIdx.x;
+    if (i >= n)
+        return;
+    const int32_t s = states[i];
+    if (s < 0 || s >= R.n) {    // (the host has checked; never out of bounds)
+        next[i] = -1;
+        return;
+    }
+    next[i] = kmc_step_lane(R, s, u[i], bad);
+}
+
+// ---- photons -------------------------------------------------------------------------------
+__device__ __forceinline__ double kmc_photon_E(const KmcDist &D, int32_t s, double u_bin,
+                                               double u_jit, double bw, double r06)
+{
+    const int64_t k = kmc_upper(D.cdf, D.off[s], D.off[s + 1], u_bin);
+    const double d = D.centres[k] + (u_jit * bw - bw / 2.0);
+    const double d2 = d * d;
+    const double d6 = d2 * d2 * d2;
+    return r06 / (r06 + d6);
+}
+
+__global__ void __launch_bounds__(KMC_WG)
+kmc_fret_probs_kernel(KmcDist D, int32_t n_states, uint64_t seed, uint64_t chain, int64_t n,
+                      const int32_t *__restrict__ states, double bw, double r06,
+                      double *__restrict__ E)
+{
+    const int64_t k = (int64_t)blockIdx.x * KMC_WG + threadIdx.x;
+    if (k >= n)
+        return;
+    const int32_t s = states[k];
+    if (s < 0 || s >= n_states || D.off[s + 1] <= D.off[s]) {   // (the host has checked)
+        E[k] = 0.0;
+        return;
+    }
+    E[k] = kmc_photon_E(D, s, kmc_uniform(seed, KMC_BIN, chain, (uint64_t)k),
+                        kmc_uniform(seed, KMC_JITTER, chain, (uint64_t)k), bw, r06);
+}
+
+// frames t0 .. t0 + m - 1 of every burst that reaches them.  cur: the state at frame t0
+// (t0 > 0), kpos: the first photon not yet served.  traj (may be null): flat, burst b's
+// states from toff[b].
+__global__ void __launch_bounds__(KMC_LANE_WG)
+kmc_burst_kernel(KmcRows R, KmcDist D, uint64_t seed, int64_t first_burst, int64_t n_bursts,
+                 const int64_t *__restrict__ foff, const int64_t *__restrict__ frames,
+                 const double *__restrict__ pop_cdf, double bw, double r06,
+                 int32_t *__restrict__ cur, int64_t *__restrict__ kpos, int64_t t0, int64_t m,
+                 uint8_t *__restrict__ photons, int32_t *__restrict__ traj,
+                 const int64_t *__restrict__ toff, uint32_t *__restrict__ bad)
+{
+    __shared__ int32_t tile[EK_WAVE][KMC_TS + 1];
+    const int lane = threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * KMC_LANE_WG + lane;
+    const bool live = b < n_bursts;
+    const uint64_t chain = (uint64_t)(first_burst + b);
+    int64_t k0 = 0, k1 = 0, last = -1, k = 0, tbase = 0;
+    int32_t s = 0;
+    if (live) {
+        k0 = foff[b];
+        k1 = foff[b + 1];
+        last = frames[k1 - 1];
+        if (traj)
+            tbase = toff[b];
+        if (t0 == 0) {
+            s = (int32_t)kmc_upper(pop_cdf, 0, R.n, kmc_uniform(seed, KMC_INIT, chain, 0));
+            k = k0;
+        } else if (t0 <= last) {
+            s = cur[b];
+            k = kpos[b];
+        }
+    }
+    const int64_t tend = last < t0 + m - 1 ? last : t0 + m - 1;    // the last frame done here
+    double u0 = 0.0, u1 = 0.0;
+    bool first = true;
+    for (int64_t tb = t0; __any(tb <= tend); tb += KMC_TS) {
+        const int64_t left = tend - tb + 1;
+        const int cnt = (int)(left < 0 ? 0 : left < KMC_TS ? left : KMC_TS);
+        for (int j = 0; j < cnt; ++j) {
+            const int64_t t = tb + j;
+            tile[lane][j] = s;
+            while (k < k1 && frames[k] == t) {
+                const uint64_t ph = (uint64_t)(k - k0);
+                const double E = kmc_photon_E(D, s, kmc_uniform(seed, KMC_BIN, chain, ph),
+                                              kmc_uniform(seed, KMC_JITTER, chain, ph), bw, r06);
+                photons[k] = kmc_uniform(seed, KMC_COIN, chain, ph) <= E ? 1 : 0;
+                ++k;
+            }
+            if (t < last) {
+                if (!(t & 1) || first)
+                    kmc_pair(seed, KMC_TRANS, chain, (uint64_t)t >> 1, u0, u1);
+                first = false;
+                s = kmc_step_lane(R, s, (t & 1) ? u1 : u0, bad);
+            }
+        }
+        if (traj) {             // (the same in every lane)
+            __syncthreads();
+            kmc_tile_flush(tile, lane, (long long)(tbase + tb), cnt, traj);
+            __syncthreads();
+        }
+    }
+    if (live && t0 + m - 1 < last) {
+        cur[b] = s;
+        kpos[b] = k;
+    }
+}
+
+// ---- ensemble ------------------------------------------------------------------------------
+__global__ void __launch_bounds__(KMC_WG)
+kmc_ens_part_kernel(const double *__restrict__ T, const double *__restrict__ p, int32_t n,
+                    double *__restrict__ part)
+{
+    const int64_t j = (int64_t)blockIdx.x * KMC_WG + threadIdx.x;
+    if (j >= n)
+        return;
+    const int64_t i0 = (int64_t)blockIdx.y * KMC_ENS_ROWS;
+    const int64_t i1 = i0 + KMC_ENS_ROWS < n ? i0 + KMC_ENS_ROWS : n;
+    double acc = 0.0;
+#pragma unroll 8
+    for (int64_t i = i0; i < i1; ++i)
+        acc = acc + p[i] * T[i * n + j];
+    part[(int64_t)blockIdx.y * n + j] = acc;
+}
+
+__global__ void __launch_bounds__(KMC_WG)
+kmc_ens_sum_kernel(const double *__restrict__ part, int32_t blocks, int32_t n,
+                   double *__restrict__ pn)
+{
+    const int64_t j = (int64_t)blockIdx.x * KMC_WG + threadIdx.x;
+    if (j >= n)
+        return;
+    double acc = 0.0;
+    for (int32_t r = 0; r < blocks; ++r)
+        acc = acc + part[(int64_t)r * n + j];
+    pn[j] = acc;
+}
+
+__global__ void __launch_bounds__(KMC_WG)
+kmc_ens_csc_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rows,
+                   const double *__restrict__ vals, const double *__restrict__ p, int32_t n,
+                   double *__restrict__ pn)
+{
+    const int64_t j = (int64_t)blockIdx.x * KMC_WG + threadIdx.x;
+    if (j >= n)
+        return;
+    double acc = 0.0;
+    for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k)
+        acc = acc + vals[k] * p[rows[k]];
+    pn[j] = acc;
+}
+
+// one workgroup: out[0] = p . o
+__global__ void __launch_bounds__(KMC_WG)
+kmc_ens_dot_kernel(const double *__restrict__ p, const double *__restrict__ o, int32_t n,
+                   double *__restrict__ out)
+{
+    __shared__ double sh[KMC_WG];
+    double acc = 0.0;
+    for (int32_t k = threadIdx.x; k < n; k += KMC_WG)
+        acc = acc + p[k] * o[k];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = KMC_WG / 2; off >= 1; off >>= 1) {
+        if ((int)threadIdx.x < off)
+            sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        out[0] = sh[0];
+}
+
+// ---- host ----------------------------------------------------------------------------------
+// what a call allocated, released whichever way the call returns
+struct KmcScope {
+    void *ptr[24];
+    int n = 0;
+    hipStream_t sync = nullptr;     // not owned: waited for before anything is freed
+    hipStream_t own = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    template <class T> hipError_t alloc(T **p, size_t bytes)
+    {
+        if (n >= 24)
+            return hipErrorOutOfMemory;
+        hipError_t e = hipMalloc((void **)p, bytes ? bytes : 1);
+        if (e == hipSuccess)
+            ptr[n++] = (void *)*p;
+        return e;
+    }
+    hipError_t events()
+    {
+        for (hipEvent_t &e : ev) {
+            hipError_t r = hipEventCreate(&e);
+            if (r != hipSuccess)
+                return r;
+        }
+        return hipSuccess;
+    }
+    ~KmcScope()
+    {
+        if (sync)
+            (void)hipStreamSynchronize(sync);
+        if (own)
+            (void)hipStreamSynchronize(own);
+        for (int i = 0; i < n; ++i)
+            (void)hipFree(ptr[i]);
+        for (hipEvent_t e : ev)
+            if (e)
+                (void)hipEventDestroy(e);
+        if (own)
+            (void)hipStreamDestroy(own);
+    }
+};
+
+struct ek_kmc {
+    int device;
+    int32_t n;
+    int64_t nnz;
+    int64_t *d_indptr;
+    int32_t *d_cols;
+    double *d_cdf;
+    hipStream_t s;
+};
+
+static KmcRows kmc_rows(const ek_kmc *h)
+{
+    KmcRows R;
+    R.indptr = h->d_indptr;
+    R.cols = h->d_cols;
+    R.cdf = h->d_cdf;
+    R.n = h->n;
+    return R;
+}
+
+static int kmc_set_device(int device)
+{
+    hipError_t e0 = hipSetDevice(device);
+    if (e0 != hipSuccess)
+        return ek_set_error(EK_EHIP, "hipSetDevice(%d): %s", device, hipGetErrorString(e0));
+    return EK_OK;
+}
+
+static unsigned kmc_blocks(int64_t items, int per) { return (unsigned)((items + per - 1) / per); }
+
+static int64_t kmc_bad(uint32_t w) { return w == KMC_NO_BAD ? (int64_t)-1 : (int64_t)w; }
+
+extern "C" int ek_kmc_create(int device, int32_t n_states, const int64_t *indptr,
+                             const int32_t *cols, const double *cdf, ek_kmc **out)
+{
+    int rc = EK_OK;
+    if (!out)
+        return ek_set_error(EK_EARG, "ek_kmc_create: null argument");
+    *out = nullptr;
+    if (n_states < 1 || !indptr || indptr[0] != 0)
+        return ek_set_error(EK_EARG, "ek_kmc_create: n_states >= 1, indptr[0] == 0");
+    for (int32_t i = 0; i < n_states; ++i)
+        if (indptr[i + 1] < indptr[i])
+            return ek_set_error(EK_EARG, "ek_kmc_create: indptr descends at row %d", i);
+    const int64_t nnz = indptr[n_states];
+    if (nnz > 0 && (!cols || !cdf))
+        return ek_set_error(EK_EARG, "ek_kmc_create: null argument");
+    for (int64_t k = 0; k < nnz; ++k)
+        if (cols[k] < 0 || cols[k] >= n_states)
+            return ek_set_error(EK_EARG, "ek_kmc_create: column %d of entry %lld is no state",
+                                cols[k], (long long)k);
+    if ((rc = kmc_set_device(device)) != EK_OK)
+        return rc;
+    const size_t ib = (size_t)(n_states + 1) * sizeof(int64_t), cb = (size_t)nnz * sizeof(int32_t),
+                 fb = (size_t)nnz * sizeof(double);
+    if ((rc = ek_mi_check_memory(ib + cb + fb, "ek_kmc_create")) != EK_OK)
+        return rc;
+    ek_kmc *h = new (std::nothrow) ek_kmc();
+    if (!h)
+        return ek_set_error(EK_ENOMEM, "ek_kmc_create: out of host memory");
+    h->device = device;
+    h->n = n_states;
+    h->nnz = nnz;
+    hipError_t e = hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&h->d_indptr, ib);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&h->d_cols, cb ? cb : 1);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&h->d_cdf, fb ? fb : 1);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(h->d_indptr, indptr, ib, hipMemcpyHostToDevice, h->s);
+    if (e == hipSuccess && nnz > 0)
+        e = hipMemcpyAsync(h->d_cols, cols, cb, hipMemcpyHostToDevice, h->s);
+    if (e == hipSuccess && nnz > 0)
+        e = hipMemcpyAsync(h->d_cdf, cdf, fb, hipMemcpyHostToDevice, h->s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(h->s);
+    if (e != hipSuccess) {
+        rc = ek_set_error(EK_EHIP, "ek_kmc_create: %s", hipGetErrorString(e));
+        (void)hipFree(h->d_indptr);
+        (void)hipFree(h->d_cols);
+        (void)hipFree(h->d_cdf);
+        if (h->s)
+            (void)hipStreamDestroy(h->s);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return EK_OK;
+}
+
+extern "C" int ek_kmc_destroy(ek_kmc *h)
+{
+    if (!h)
+        return EK_OK;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->s);
+    (void)hipFree(h->d_indptr);
+    (void)hipFree(h->d_cols);
+    (void)hipFree(h->d_cdf);
+    (void)hipStreamDestroy(h->s);
+    delete h;
+    return EK_OK;
+}
+
+static int kmc_store_ms(KmcScope &sc)
+{
+    float ms = 0.f;
+    for (int q = 0; q < 3; ++q) {
+        KMC_HIP(hipEventElapsedTime(&ms, sc.ev[q], sc.ev[q + 1]));
+        kmc_ms[q] = ms;
+    }
+    return EK_OK;
+}
+
+extern "C" int ek_kmc_next(ek_kmc *h, int64_t n, const int32_t *states, const double *u,
+                           int32_t *next_out, int64_t *bad_out)
+{
+    int rc = EK_OK;
+    if (!h || n < 1 || n > ((int64_t)1 << 36) || !states || !u || !next_out || !bad_out)
+        return ek_set_error(EK_EARG, "ek_kmc_next: bad argument (1 <= n <= 2^36)");
+    if ((rc = kmc_set_device(h->device)) != EK_OK ||
+        (rc = ek_mi_check_memory((size_t)n * 16 + 256, "ek_kmc_next")) != EK_OK)
+        return rc;
+    KmcScope sc;
+    sc.sync = h->s;
+    int32_t *d_s = nullptr, *d_next = nullptr;
+    double *d_u = nullptr;
+    uint32_t *d_bad = nullptr, bad = KMC_NO_BAD;
+    KMC_HIP(sc.events());
+    KMC_HIP(sc.alloc(&d_s, (size_t)n * sizeof(int32_t)));
+    KMC_HIP(sc.alloc(&d_next, (size_t)n * sizeof(int32_t)));
+    KMC_HIP(sc.alloc(&d_u, (size_t)n * sizeof(double)));
+    KMC_HIP(sc.alloc(&d_bad, sizeof(uint32_t)));
+    KMC_HIP(hipEventRecord(sc.ev[0], h->s));
+    KMC_HIP(hipMemcpyAsync(d_s, states, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->s));
+    KMC_HIP(hipMemcpyAsync(d_u, u, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->s));
+    KMC_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(uint32_t), h->s));
+    KMC_HIP(hipEventRecord(sc.ev[1], h->s));
+    hipLaunchKernelGGL(kmc_next_kernel, dim3(kmc_blocks(n, KMC_WG)), dim3(KMC_WG), 0, h->s,
+                       kmc_rows(h), n, d_s, d_u, d_next, d_bad);
+    KMC_HIP(hipGetLastError());
+    KMC_HIP(hipEventRecord(sc.ev[2], h->s));
+    KMC_HIP(hipMemcpyAsync(next_out, d_next, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                           h->s));
+    KMC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, h->s));
+    KMC_HIP(hipEventRecord(sc.ev[3], h->s));
+    KMC_HIP(hipStreamSynchronize(h->s));
+    *bad_out = kmc_bad(bad);
+    return kmc_store_ms(sc);
+}
+
+extern "C" int ek_kmc_trajectories(ek_kmc *h, uint64_t seed, int64_t first_chain,
+                                   int64_t n_chains, const int32_t *start_states,
+                                   int64_t n_steps, int32_t form, int64_t step_cap, int32_t *out,
+                                   int64_t *bad_out)
+{
+    int rc = EK_OK;
+    if (!h || !start_states || !out || !bad_out || n_chains < 1 || n_steps < 1 ||
+        first_chain < 0 || n_chains > ((int64_t)1 << 31) || step_cap < 0 || form < 0 || form > 2 ||
+        first_chain > ((int64_t)1 << 60) - n_chains || n_steps > ((int64_t)1 << 62) / n_chains)
+        return ek_set_error(EK_EARG, "ek_kmc_trajectories: bad argument (1 <= n_chains <= 2^31, "
+                                     "n_steps >= 1, chains below 2^60, form 0 .. 2, step_cap >= 0)");
+    for (int64_t c = 0; c < n_chains; ++c)
+        if (start_states[c] < 0 || start_states[c] >= h->n)
+            return ek_set_error(EK_EARG, "ek_kmc_trajectories: start state %d of chain %lld is "
+                                         "no state of %d", start_states[c], (long long)c, h->n);
+    *bad_out = -1;
+    for (int64_t c = 0; c < n_chains; ++c)
+        out[c * n_steps] = start_states[c];
+    kmc_ms[0] = kmc_ms[1] = kmc_ms[2] = 0.0;
+    const int64_t draws = n_steps - 1;
+    if (draws == 0)
+        return EK_OK;
+    if ((rc = kmc_set_device(h->device)) != EK_OK)
+        return rc;
+    const int64_t cap = step_cap > 0 ? step_cap : KMC_STEP_CAP;
+    const bool wave = form == 2 || (form == 0 && n_chains <= KMC_WAVE_MAX_CHAINS);
+    // the buffer [nc chains][mc steps]: all chains and as many steps as fit; once fewer
+    // than KMC_MIN_CHUNK steps would fit, fewer chains
+    const int64_t cells = KMC_BUF_BYTES / (int64_t)sizeof(int32_t);
+    int64_t mc = cells / n_chains;
+    if (mc < KMC_MIN_CHUNK)
+        mc = KMC_MIN_CHUNK;
+    if (mc > draws)
+        mc = draws;
+    int64_t nc = cells / mc;
+    if (nc > n_chains)
+        nc = n_chains;
+    if ((rc = ek_mi_check_memory((size_t)(nc * mc + nc) * sizeof(int32_t) + 256,
+                                 "ek_kmc_trajectories")) != EK_OK)
+        return rc;
+    KmcScope sc;
+    sc.sync = h->s;
+    int32_t *d_buf = nullptr, *d_cur = nullptr;
+    uint32_t *d_bad = nullptr, bad = KMC_NO_BAD;
+    float ms = 0.f;
+    KMC_HIP(sc.events());
+    KMC_HIP(sc.alloc(&d_buf, (size_t)(nc * mc) * sizeof(int32_t)));
+    KMC_HIP(sc.alloc(&d_cur, (size_t)nc * sizeof(int32_t)));
+    KMC_HIP(sc.alloc(&d_bad, sizeof(uint32_t)));
+    KMC_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(uint32_t), h->s));
+    for (int64_t c0 = 0; c0 < n_chains; c0 += nc) {
+        const int64_t ncc = n_chains - c0 < nc ? n_chains - c0 : nc;
+        KMC_HIP(hipEventRecord(sc.ev[0], h->s));
+        KMC_HIP(hipMemcpyAsync(d_cur, start_states + c0, (size_t)ncc * sizeof(int32_t),
+                               hipMemcpyHostToDevice, h->s));
+        KMC_HIP(hipEventRecord(sc.ev[1], h->s));
+        KMC_HIP(hipStreamSynchronize(h->s));
+        KMC_HIP(hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
+        kmc_ms[0] += ms;
+        for (int64_t ts = 0; ts < draws; ts += mc) {
+            const int64_t mcc = draws - ts < mc ? draws - ts : mc;
+            KMC_HIP(hipEventRecord(sc.ev[1], h->s));
+            for (int64_t l0 = 0; l0 < mcc; l0 += cap) {
+                const int64_t lm = mcc - l0 < cap ? mcc - l0 : cap;
+                if (wave)
+                    hipLaunchKernelGGL(kmc_wave_kernel,
+                                       dim3(kmc_blocks(ncc, KMC_WAVE_WG / EK_WAVE)),
+                                       dim3(KMC_WAVE_WG), 0, h->s, kmc_rows(h), seed,
+                                       first_chain + c0, ncc, d_cur, ts + l0, lm, d_buf, mc, l0,
+                                       d_bad);
+                else
+                    hipLaunchKernelGGL(kmc_lane_kernel, dim3(kmc_blocks(ncc, KMC_LANE_WG)),
+                                       dim3(KMC_LANE_WG), 0, h->s, kmc_rows(h), seed,
+                                       first_chain + c0, ncc, d_cur, ts + l0, lm, d_buf, mc, l0,
+                                       d_bad);
+                KMC_HIP(hipGetLastError());
+            }
+            KMC_HIP(hipEventRecord(sc.ev[2], h->s));
+            KMC_HIP(hipMemcpy2DAsync(out + c0 * n_steps + 1 + ts, (size_t)n_steps * sizeof(int32_t),
+                                     d_buf, (size_t)mc * sizeof(int32_t),
+                                     (size_t)mcc * sizeof(int32_t), (size_t)ncc,
+                                     hipMemcpyDeviceToHost, h->s));
+            KMC_HIP(hipEventRecord(sc.ev[3], h->s));
+            KMC_HIP(hipStreamSynchronize(h->s));
+            KMC_HIP(hipEventElapsedTime(&ms, sc.ev[1], sc.ev[2]));
+            kmc_ms[1] += ms;
+            KMC_HIP(hipEventElapsedTime(&ms, sc.ev[2], sc.ev[3]));
+            kmc_ms[2] += ms;
+        }
+    }
+    KMC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, h->s));
+    KMC_HIP(hipStreamSynchronize(h->s));
+    *bad_out = kmc_bad(bad);
+    return EK_OK;
+}
+
+// ---- ensemble ------------------------------------------------------------------------------
+extern "C" int ek_kmc_ensemble(int device, int32_t n, const double *T, const int64_t *colptr,
+                               const int32_t *rows, const double *vals, const double *p0,
+                               int64_t n_steps, const double *observable, double *p_out,
+                               double *out)
+{
+    int rc = EK_OK;
+    const bool dense = T != nullptr;
+    if (n < 1 || n_steps < 1 || !p0 || !p_out || !out || (dense == (colptr != nullptr)) ||
+        n_steps > ((int64_t)1 << 40) / n)
+        return ek_set_error(EK_EARG, "ek_kmc_ensemble: bad argument (n, n_steps >= 1, either T "
+                                     "or colptr / rows / vals)");
+    int64_t nnz = 0;
+    if (!dense) {
+        if (colptr[0] != 0)
+            return ek_set_error(EK_EARG, "ek_kmc_ensemble: colptr[0] != 0");
+        for (int32_t j = 0; j < n; ++j)
+            if (colptr[j + 1] < colptr[j])
+                return ek_set_error(EK_EARG, "ek_kmc_ensemble: colptr descends at column %d", j);
+        nnz = colptr[n];
+        if (nnz > 0 && (!rows || !vals))
+            return ek_set_error(EK_EARG, "ek_kmc_ensemble: null argument");
+        for (int64_t k = 0; k < nnz; ++k)
+            if (rows[k] < 0 || rows[k] >= n)
+                return ek_set_error(EK_EARG, "ek_kmc_ensemble: row %d of entry %lld is no state",
+                                    rows[k], (long long)k);
+    }
+    if ((rc = kmc_set_device(device)) != EK_OK)
+        return rc;
+    const size_t nb = (size_t)n * sizeof(double);
+    const int32_t blocks = (n + KMC_ENS_ROWS - 1) / KMC_ENS_ROWS;
+    const size_t mat_b = dense ? (size_t)n * n * sizeof(double) + (size_t)blocks * nb
+                               : (size_t)(n + 1) * sizeof(int64_t) + (size_t)nnz * 12;
+    // every p stays on the device ([n_steps][n]), or two of them and the [n_steps] products
+    const size_t keep_b = observable ? 3 * nb + (size_t)n_steps * sizeof(double)
+                                     : (size_t)n_steps * nb;
+    if ((rc = ek_mi_check_memory(mat_b + keep_b + 1024, "ek_kmc_ensemble")) != EK_OK)
+        return rc;
+    KmcScope sc;
+    double *d_T = nullptr, *d_part = nullptr, *d_vals = nullptr, *d_p = nullptr, *d_o = nullptr,
+           *d_obs = nullptr;
+    int64_t *d_colptr = nullptr;
+    int32_t *d_rows = nullptr;
+    KMC_HIP(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
+    hipStream_t s = sc.own;
+    KMC_HIP(sc.events());
+    if (dense) {
+        KMC_HIP(sc.alloc(&d_T, (size_t)n * n * sizeof(double)));
+        KMC_HIP(sc.alloc(&d_part, (size_t)blocks * nb));
+    } else {
+        KMC_HIP(sc.alloc(&d_colptr, (size_t)(n + 1) * sizeof(int64_t)));
+        KMC_HIP(sc.alloc(&d_rows, (size_t)nnz * sizeof(int32_t)));
+        KMC_HIP(sc.alloc(&d_vals, (size_t)nnz * sizeof(double)));
+    }
+    KMC_HIP(sc.alloc(&d_p, observable ? 2 * nb : (size_t)n_steps * nb));
+    if (observable) {
+        KMC_HIP(sc.alloc(&d_o, nb));
+        KMC_HIP(sc.alloc(&d_obs, (size_t)n_steps * sizeof(double)));
+    }
+    KMC_HIP(hipEventRecord(sc.ev[0], s));
+    if (dense) {
+        KMC_HIP(hipMemcpyAsync(d_T, T, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s));
+    } else {
+        KMC_HIP(hipMemcpyAsync(d_colptr, colptr, (size_t)(n + 1) * sizeof(int64_t),
+                               hipMemcpyHostToDevice, s));
+        if (nnz > 0) {
+            KMC_HIP(hipMemcpyAsync(d_rows, rows, (size_t)nnz * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, s));
+            KMC_HIP(hipMemcpyAsync(d_vals, vals, (size_t)nnz * sizeof(double),
+                                   hipMemcpyHostToDevice, s));
+        }
+    }
+    KMC_HIP(hipMemcpyAsync(d_p, p0, nb, hipMemcpyHostToDevice, s));
+    if (observable)
+        KMC_HIP(hipMemcpyAsync(d_o, observable, nb, hipMemcpyHostToDevice, s));
+    KMC_HIP(hipEventRecord(sc.ev[1], s));
+    {
+        const dim3 wg(KMC_WG), gcol(kmc_blocks(n, KMC_WG));
+        double *p = d_p;
+        for (int64_t t = 0; t < n_steps; ++t) {
+            if (observable)
+                hipLaunchKernelGGL(kmc_ens_dot_kernel, dim3(1), wg, 0, s, p, d_o, n, d_obs + t);
+            if (t + 1 == n_steps)
+                break;
+            double *pn = observable ? (p == d_p ? d_p + n : d_p) : p + n;
+            if (dense) {
+                hipLaunchKernelGGL(kmc_ens_part_kernel, dim3(gcol.x, (unsigned)blocks), wg, 0, s,
+                                   d_T, p, n, d_part);
+                hipLaunchKernelGGL(kmc_ens_sum_kernel, gcol, wg, 0, s, d_part, blocks, n, pn);
+            } else {
+                hipLaunchKernelGGL(kmc_ens_csc_kernel, gcol, wg, 0, s, d_colptr, d_rows, d_vals,
+                                   p, n, pn);
+            }
+            p = pn;
+        }
+        KMC_HIP(hipGetLastError());
+        KMC_HIP(hipEventRecord(sc.ev[2], s));
+        KMC_HIP(hipMemcpyAsync(p_out, p, nb, hipMemcpyDeviceToHost, s));
+        if (observable)
+            KMC_HIP(hipMemcpyAsync(out, d_obs, (size_t)n_steps * sizeof(double),
+                                   hipMemcpyDeviceToHost, s));
+        else
+            KMC_HIP(hipMemcpyAsync(out, d_p, (size_t)n_steps * nb, hipMemcpyDeviceToHost, s));
+    }
+    KMC_HIP(hipEventRecord(sc.ev[3], s));
+    KMC_HIP(hipStreamSynchronize(s));
+    return kmc_store_ms(sc);
+}
+
+// ---- photons -------------------------------------------------------------------------------
+// the per-state distance tables: every state has a bin, the offsets ascend
+static int kmc_check_dist(int32_t n_states, const int64_t *dist_off, const double *centres,
+                          const double *dist_cdf, const char *who)
+{
+    if (n_states < 1 || !dist_off || !centres || !dist_cdf || dist_off[0] != 0)
+        return ek_set_error(EK_EARG, "%s: null distance tables or dist_off[0] != 0", who);
+    for (int32_t i = 0; i < n_states; ++i)
+        if (dist_off[i + 1] <= dist_off[i])
+            return ek_set_error(EK_EARG, "%s: state %d has no distance bin", who, i);
+    return EK_OK;
+}
+
+static int kmc_upload_dist(KmcScope &sc, hipStream_t s, int32_t n_states, const int64_t *dist_off,
+                           const double *centres, const double *dist_cdf, KmcDist *D)
+{
+    int64_t *d_off = nullptr;
+    double *d_c = nullptr, *d_f = nullptr;
+    const size_t ob = (size_t)(n_states + 1) * sizeof(int64_t),
+                 bb = (size_t)dist_off[n_states] * sizeof(double);
+    KMC_HIP(sc.alloc(&d_off, ob));
+    KMC_HIP(sc.alloc(&d_c, bb));
+    KMC_HIP(sc.alloc(&d_f, bb));
+    KMC_HIP(hipMemcpyAsync(d_off, dist_off, ob, hipMemcpyHostToDevice, s));
+    KMC_HIP(hipMemcpyAsync(d_c, centres, bb, hipMemcpyHostToDevice, s));
+    KMC_HIP(hipMemcpyAsync(d_f, dist_cdf, bb, hipMemcpyHostToDevice, s));
+    D->off = d_off;
+    D->centres = d_c;
+    D->cdf = d_f;
+    return EK_OK;
+}
+
+extern "C" int ek_kmc_fret_probs(int device, uint64_t seed, int64_t chain, int64_t n,
+                                 const int32_t *states, int32_t n_states, const int64_t *dist_off,
+                                 const double *centres, const double *dist_cdf, double bin_width,
+                                 double r06, double *E_out)
+{
+    int rc = EK_OK;
+    if (n < 1 || n > ((int64_t)1 << 36) || !states || !E_out || chain < 0 ||
+        chain >= ((int64_t)1 << 60))
+        return ek_set_error(EK_EARG, "ek_kmc_fret_probs: bad argument (1 <= n <= 2^36, 0 <= "
+                                     "chain < 2^60)");
+    if ((rc = kmc_check_dist(n_states, dist_off, centres, dist_cdf, "ek_kmc_fret_probs")) != EK_OK)
+        return rc;
+    for (int64_t k = 0; k < n; ++k)
+        if (states[k] < 0 || states[k] >= n_states)
+            return ek_set_error(EK_EARG, "ek_kmc_fret_probs: state %d of photon %lld is no "
+                                         "state of %d", states[k], (long long)k, n_states);
+    if ((rc = kmc_set_device(device)) != EK_OK ||
+        (rc = ek_mi_check_memory((size_t)n * 12 + (size_t)dist_off[n_states] * 16 +
+                                 (size_t)n_states * 8 + 1024, "ek_kmc_fret_probs")) != EK_OK)
+        return rc;
+    KmcScope sc;
+    KmcDist D;
+    int32_t *d_s = nullptr;
+    double *d_E = nullptr;
+    KMC_HIP(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
+    hipStream_t s = sc.own;
+    KMC_HIP(sc.events());
+    KMC_HIP(sc.alloc(&d_s, (size_t)n * sizeof(int32_t)));
+    KMC_HIP(sc.alloc(&d_E, (size_t)n * sizeof(double)));
+    KMC_HIP(hipEventRecord(sc.ev[0], s));
+    if ((rc = kmc_upload_dist(sc, s, n_states, dist_off, centres, dist_cdf, &D)) != EK_OK)
+        return rc;
+    KMC_HIP(hipMemcpyAsync(d_s, states, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    KMC_HIP(hipEventRecord(sc.ev[1], s));
+    hipLaunchKernelGGL(kmc_fret_probs_kernel, dim3(kmc_blocks(n, KMC_WG)), dim3(KMC_WG), 0, s, D,
+                       n_states, seed, (uint64_t)chain, n, d_s, bin_width, r06, d_E);
+    KMC_HIP(hipGetLastError());
+    KMC_HIP(hipEventRecord(sc.ev[2], s));
+    KMC_HIP(hipMemcpyAsync(E_out, d_E, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    KMC_HIP(hipEventRecord(sc.ev[3], s));
+    KMC_HIP(hipStreamSynchronize(s));
+    return kmc_store_ms(sc);
+}
+
+extern "C" int ek_kmc_fret_bursts(ek_kmc *h, uint64_t seed, int64_t first_burst,
+                                  int64_t n_bursts, const int64_t *frame_off,
+                                  const int64_t *frames, const double *pop_cdf,
+                                  const int64_t *dist_off, const double *centres,
+                                  const double *dist_cdf, double bin_width, double r06,
+                                  int64_t step_cap, uint8_t *photons_out, int32_t *traj_out,
+                                  int64_t *bad_out)
+{
+    int rc = EK_OK;
+    if (!h || !frame_off || !frames || !pop_cdf || !photons_out || !bad_out || n_bursts < 1 ||
+        n_bursts > ((int64_t)1 << 31) || first_burst < 0 || step_cap < 0 ||
+        first_burst > ((int64_t)1 << 60) - n_bursts || frame_off[0] != 0)
+        return ek_set_error(EK_EARG, "ek_kmc_fret_bursts: bad argument (1 <= n_bursts <= 2^31, "
+                                     "chains below 2^60, frame_off[0] == 0, step_cap >= 0)");
+    if ((rc = kmc_check_dist(h->n, dist_off, centres, dist_cdf, "ek_kmc_fret_bursts")) != EK_OK)
+        return rc;
+    int64_t max_last = 0, traj_cells = 0;
+    for (int64_t b = 0; b < n_bursts; ++b) {
+        if (frame_off[b + 1] <= frame_off[b])
+            return ek_set_error(EK_EARG, "ek_kmc_fret_bursts: burst %lld has no photon",
+                                (long long)b);
+        int64_t prev = 0;
+        for (int64_t k = frame_off[b]; k < frame_off[b + 1]; ++k) {
+            if (frames[k] < prev || frames[k] >= ((int64_t)1 << 40))
+                return ek_set_error(EK_EARG, "ek_kmc_fret_bursts: the frames of burst %lld are "
+                                             "negative, decrease or exceed 2^40", (long long)b);
+            prev = frames[k];
+        }
+        max_last = prev > max_last ? prev : max_last;
+        traj_cells += prev + 1;
+    }
+    *bad_out = -1;
+    if ((rc = kmc_set_device(h->device)) != EK_OK)
+        return rc;
+    const int64_t n_ph = frame_off[n_bursts];
+    const size_t tb = traj_out ? (size_t)traj_cells * sizeof(int32_t) + (size_t)(n_bursts + 1) * 8
+                               : 0;
+    if ((rc = ek_mi_check_memory(tb + (size_t)n_ph * 9 + (size_t)n_bursts * 20 +
+                                 (size_t)h->n * 16 + (size_t)dist_off[h->n] * 16 + 1024,
+                                 "ek_kmc_fret_bursts")) != EK_OK)
+        return rc;
+    const int64_t cap = step_cap > 0 ? step_cap : KMC_STEP_CAP;
+    KmcScope sc;
+    sc.sync = h->s;
+    hipStream_t s = h->s;
+    KmcDist D;
+    int64_t *d_foff = nullptr, *d_frames = nullptr, *d_kpos = nullptr, *d_toff = nullptr;
+    double *d_pop = nullptr;
+    int32_t *d_cur = nullptr, *d_traj = nullptr;
+    uint8_t *d_ph = nullptr;
+    uint32_t *d_bad = nullptr, bad = KMC_NO_BAD;
+    int64_t *toff = nullptr;
+    KMC_HIP(sc.events());
+    KMC_HIP(sc.alloc(&d_foff, (size_t)(n_bursts + 1) * sizeof(int64_t)));
+    KMC_HIP(sc.alloc(&d_frames, (size_t)n_ph * sizeof(int64_t)));
+    KMC_HIP(sc.alloc(&d_kpos, (size_t)n_bursts * sizeof(int64_t)));
+    KMC_HIP(sc.alloc(&d_cur, (size_t)n_bursts * sizeof(int32_t)));
+    KMC_HIP(sc.alloc(&d_pop, (size_t)h->n * sizeof(double)));
+    KMC_HIP(sc.alloc(&d_ph, (size_t)n_ph));
+    KMC_HIP(sc.alloc(&d_bad, sizeof(uint32_t)));
+    if (traj_out) {
+        KMC_HIP(sc.alloc(&d_traj, (size_t)traj_cells * sizeof(int32_t)));
+        KMC_HIP(sc.alloc(&d_toff, (size_t)(n_bursts + 1) * sizeof(int64_t)));
+        toff = new (std::nothrow) int64_t[n_bursts + 1];
+        if (!toff)
+            return ek_set_error(EK_ENOMEM, "ek_kmc_fret_bursts: out of host memory");
+        toff[0] = 0;
+        for (int64_t b = 0; b < n_bursts; ++b)
+            toff[b + 1] = toff[b] + frames[frame_off[b + 1] - 1] + 1;
+    }
+    rc = [&]() -> int {
+        KMC_HIP(hipEventRecord(sc.ev[0], s));
+        int rc2 = kmc_upload_dist(sc, s, h->n, dist_off, centres, dist_cdf, &D);
+        if (rc2 != EK_OK)
+            return rc2;
+        KMC_HIP(hipMemcpyAsync(d_foff, frame_off, (size_t)(n_bursts + 1) * sizeof(int64_t),
+                               hipMemcpyHostToDevice, s));
+        KMC_HIP(hipMemcpyAsync(d_frames, frames, (size_t)n_ph * sizeof(int64_t),
+                               hipMemcpyHostToDevice, s));
+        KMC_HIP(hipMemcpyAsync(d_pop, pop_cdf, (size_t)h->n * sizeof(double),
+                               hipMemcpyHostToDevice, s));
+        if (traj_out)
+            KMC_HIP(hipMemcpyAsync(d_toff, toff, (size_t)(n_bursts + 1) * sizeof(int64_t),
+                                   hipMemcpyHostToDevice, s));
+        KMC_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(uint32_t), s));
+        KMC_HIP(hipStreamSynchronize(s));      // (toff is released when this returns)
+        KMC_HIP(hipEventRecord(sc.ev[1], s));
+        for (int64_t t0 = 0; t0 <= max_last; t0 += cap) {
+            hipLaunchKernelGGL(kmc_burst_kernel, dim3(kmc_blocks(n_bursts, KMC_LANE_WG)),
+                               dim3(KMC_LANE_WG), 0, s, kmc_rows(h), D, seed, first_burst,
+                               n_bursts, d_foff, d_frames, d_pop, bin_width, r06, d_cur, d_kpos,
+                               t0, cap, d_ph, d_traj, d_toff, d_bad);
+            KMC_HIP(hipGetLastError());
+        }
+        KMC_HIP(hipEventRecord(sc.ev[2], s));
+        KMC_HIP(hipMemcpyAsync(photons_out, d_ph, (size_t)n_ph, hipMemcpyDeviceToHost, s));
+        if (traj_out)
+            KMC_HIP(hipMemcpyAsync(traj_out, d_traj, (size_t)traj_cells * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, s));
+        KMC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        KMC_HIP(hipEventRecord(sc.ev[3], s));
+        KMC_HIP(hipStreamSynchronize(s));
+        return kmc_store_ms(sc);
+    }();
+    delete[] toff;
+    if (rc == EK_OK)
+        *bad_out = kmc_bad(bad);
+    return rc;
+}
+
+extern "C" int ek_kmc_last_timing(double *ms_out)
+{
+    if (!ms_out)
+        return ek_set_error(EK_EARG, "ek_kmc_last_timing: null argument");
+    for (int i = 0; i < 3; ++i)
+        ms_out[i] = kmc_ms[i];
+    return EK_OK;
+}

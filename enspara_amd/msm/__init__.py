@@ -7,3 +7,4 @@ from .msm import MSM  # noqa: F401
 from .timescales import implied_timescales  # noqa: F401
 from .trimming import TrimMapping, trim_disconnected  # noqa: F401
 from . import bace  # noqa: F401  (a module, as in the reference: msm.bace.bace)
+from . import synthetic_data  # noqa: F401  (a module, as in the reference)

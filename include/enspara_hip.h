@@ -834,6 +834,66 @@ int ek_ent_state_counts_read(ek_ent_state_counts *h, uint64_t *counts_out);
 int ek_ent_state_counts_last_timing(ek_ent_state_counts *h, double *ms_out);
 int ek_ent_state_counts_close(ek_ent_state_counts *h);
 
+/* ---- kinetic Monte Carlo on a transition matrix, smFRET bursts, ensembles ------------
+ * Replaces enspara/msm/synthetic_data.py and the burst sampling of
+ * enspara/geometry/dyes_from_expt_dist.py (csrc/ek_kmc.hip).  All arrays
+ * are host memory.
+ * Uniforms: Philox4x32-10, key = seed (low word first), counter = {i lo, i hi, chain lo,
+ * stream << 28 | chain hi} with i = index >> 1; the call's words a, b, c, d give the
+ * doubles ((a >> 5) * 2^26 + (b >> 6)) * 2^-53 (index even) and the same of c, d (index
+ * odd).  Streams: 0 transition (index = the step left), 1 initial state (index 0), 2
+ * distance bin, 3 in-bin jitter, 4 photon coin (index = the photon within its burst).
+ * chain < 2^60.  What a chain draws depends on (seed, chain, index) alone.
+ * ek_kmc_create: the rows of T compressed to their nonzeros: indptr [n_states + 1], cols
+ * [nnz] ascending within a row, cdf [nnz] = cumsum(nonzeros of the row) / its last (so
+ * every row's last cdf is 1.0).  A row may be empty.  EK_EARG if indptr does not
+ * ascend from 0 or a column is no state.
+ * ek_kmc_next: next_out[i] = the column of the first cdf entry of row states[i] that is
+ * > u[i] (0 <= u < 1 and states in range: the caller checks; the kernel clamps).
+ * bad_out: -1, or the smallest state with an empty row that had to step.
+ * ek_kmc_trajectories: out [n_chains][n_steps]; out[c][0] = start_states[c], out[c][t + 1]
+ * = one step from out[c][t] with the transition double of (chain first_chain + c, index
+ * t).  form: 0 the library chooses, 1 a lane per chain (binary search), 2 a wave per
+ * chain (64 pivots and a ballot per round); the states do not depend on it, nor on
+ * step_cap (> 0: steps per launch; 0: the default), nor on how the chains are split
+ * into calls.  bad_out as above; the chain stays where it is.
+ * ek_kmc_ensemble: p <- p T repeated n_steps - 1 times, p0 [n] first.  T [n][n] dense
+ * row-major (colptr null), or column-compressed colptr [n + 1], rows, vals (T null).
+ * observable null: out [n_steps][n] = every p; else out [n_steps] = p . observable.
+ * p_out [n] = the last p.  Fixed summation order (csrc/ek_kmc.hip), no float atomics.
+ * ek_kmc_fret_probs: E_out[k] = r06 / (r06 + d^6) with d = the centre of the bin picked
+ * by inverse CDF (dist_cdf, per state dist_off [n_states + 1]) with the bin double of
+ * (chain, k) + jitter double * bin_width - bin_width / 2, d^6 = (d d)(d d)(d d).
+ * ek_kmc_fret_bursts: burst b (chain first_burst + b) has the photons frame_off[b] ..
+ * frame_off[b + 1] at the frames `frames` (>= 0, not decreasing, at least one).  Its
+ * chain starts at the inverse CDF pop_cdf [n_states] of the initial double and runs to
+ * its last frame; photons_out[k] = 1 iff the coin double <= E of photon k.  traj_out
+ * null, or the chains' states, burst after burst (last frame + 1 each), flat.
+ * ek_kmc_last_timing: ms_out[3] = upload, kernels, download of the last call. */
+typedef struct ek_kmc ek_kmc;
+int ek_kmc_create(int device, int32_t n_states, const int64_t *indptr, const int32_t *cols,
+                  const double *cdf, ek_kmc **out);
+int ek_kmc_destroy(ek_kmc *h);
+int ek_kmc_next(ek_kmc *h, int64_t n, const int32_t *states, const double *u,
+                int32_t *next_out, int64_t *bad_out);
+int ek_kmc_trajectories(ek_kmc *h, uint64_t seed, int64_t first_chain, int64_t n_chains,
+                        const int32_t *start_states, int64_t n_steps, int32_t form,
+                        int64_t step_cap, int32_t *out, int64_t *bad_out);
+int ek_kmc_ensemble(int device, int32_t n, const double *T, const int64_t *colptr,
+                    const int32_t *rows, const double *vals, const double *p0,
+                    int64_t n_steps, const double *observable, double *p_out, double *out);
+int ek_kmc_fret_probs(int device, uint64_t seed, int64_t chain, int64_t n,
+                      const int32_t *states, int32_t n_states, const int64_t *dist_off,
+                      const double *centres, const double *dist_cdf, double bin_width,
+                      double r06, double *E_out);
+int ek_kmc_fret_bursts(ek_kmc *h, uint64_t seed, int64_t first_burst, int64_t n_bursts,
+                       const int64_t *frame_off, const int64_t *frames,
+                       const double *pop_cdf, const int64_t *dist_off, const double *centres,
+                       const double *dist_cdf, double bin_width, double r06,
+                       int64_t step_cap, uint8_t *photons_out, int32_t *traj_out,
+                       int64_t *bad_out);
+int ek_kmc_last_timing(double *ms_out);
+
 /* ---- dihedral angles and buffered rotamer states ------------------------------------
  * Replaces enspara/geometry/rotamer.py (csrc/ek_rotamer.hip).  All arrays are host
  * memory.  A dihedral is of one of n_kinds kinds (kind [n] bytes); kind k has

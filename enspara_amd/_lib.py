@@ -6,6 +6,7 @@ that the library binds to the HIP runtime torch already loaded (both carry
 the soname libamdhip64.so.7); torch itself is only plumbing here
 (torch.distributed for the multi-GPU exchange).
 """
+import collections
 import ctypes as C
 import os
 
@@ -82,6 +83,7 @@ SYMBOLS = [
     "ek_debug_guards",
     "ek_timing_begin", "ek_timing_end", "ek_timing_form", "ek_hbm_copy_rate",
     "ek_qcp_probe",
+    "ek_live_resources", "ek_fail_alloc_at",
 ]
 
 
@@ -361,6 +363,9 @@ def load():
     L.ek_timing_form.argtypes = [vp, i32p]
     L.ek_hbm_copy_rate.argtypes = [C.c_int, C.c_size_t, f64p]
     L.ek_qcp_probe.argtypes = [C.c_int, vp, vp, vp, i32, vp, C.c_int64, vp, vp, vp]
+    L.ek_live_resources.argtypes = [i64p]
+    L.ek_fail_alloc_at.argtypes = [i64]
+    L.ek_fail_alloc_at.restype = i64
     for name in SYMBOLS:
         if name == "ek_debug_guards" and os.environ.get("ENSPARA_HIP_LIB"):
             continue        # (a variant library from before it: tools/)
@@ -373,6 +378,27 @@ def check(rc):
     if rc != 0:
         msg = load().ek_last_error().decode("utf-8", "replace")
         raise HipError("enspara_hip error %d: %s" % (rc, msg))
+
+
+LiveResources = collections.namedtuple(
+    "LiveResources", ["dev_allocs", "dev_bytes", "pinned_allocs", "pinned_bytes",
+                      "streams", "events", "dev_allocs_total"])
+
+
+def live_resources():
+    """What the library holds right now, counted inside it (ek_live_resources):
+    live device / pinned allocations and their bytes, live streams and events,
+    and the monotonic count of device allocations since it was loaded."""
+    out = (C.c_int64 * 7)()
+    check(load().ek_live_resources(out))
+    return LiveResources(*[int(v) for v in out])
+
+
+def fail_alloc_at(k):
+    """Test aid (ek_fail_alloc_at): the k-th device allocation from now fails
+    once, without touching the device; k < 0 disarms.  Returns the arm that was
+    pending (-1: none)."""
+    return int(load().ek_fail_alloc_at(int(k)))
 
 
 def f32p(a):

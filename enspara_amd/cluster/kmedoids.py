@@ -164,8 +164,9 @@ def _kmedoids_iterations(X, distance_method, n_iters, cluster_center_inds,
         own = store is None
         if own:
             store = FrameStore.from_array(as_xyz(X))
-            store.upload_state(distances, assignments)
         try:
+            if own:
+                store.upload_state(distances, assignments)
             return _kmedoids_iterations_device(
                 X, store, n_iters, cluster_center_inds, proposals,
                 random_state)

@@ -93,7 +93,7 @@ int ek_ensure_qtiles(ek_ctx *c)
     if (c->qt_valid)
         return EK_OK;
     if (!c->qtiles) {
-        hipError_t e = hipMalloc(
+        hipError_t e = ek_dev_malloc(
             (void **)&c->qtiles, ek_quad_tiles_bytes(std::max<int64_t>(c->n_tiles, 1), c->A));
         if (e == hipErrorOutOfMemory && c->stage_frames > 0) {
             // the upload's staging buffers (two pinned, two on the device, up to
@@ -102,13 +102,13 @@ int ek_ensure_qtiles(ek_ctx *c)
             (void)hipGetLastError();
             (void)hipStreamSynchronize(c->stream);
             for (int b = 0; b < 2; ++b) {
-                (void)hipFree(c->stage[b]);
-                (void)hipHostFree(c->pin[b]);
+                (void)ek_dev_free(c->stage[b]);
+                (void)ek_pinned_free(c->pin[b]);
                 c->stage[b] = c->pin[b] = nullptr;
                 c->up_busy[b] = false;
             }
             c->stage_frames = 0;
-            e = hipMalloc((void **)&c->qtiles,
+            e = ek_dev_malloc((void **)&c->qtiles,
                           ek_quad_tiles_bytes(std::max<int64_t>(c->n_tiles, 1), c->A));
         }
         if (e == hipErrorOutOfMemory) {
@@ -178,7 +178,7 @@ hipError_t ek_uncached_alloc(int device, void **ptr, size_t bytes)
     }
     // (whole 64 KB: fewer sizes, more reuse)
     const size_t rounded = (bytes + 65535) & ~(size_t)65535;
-    const hipError_t e = hipExtMallocWithFlags(ptr, rounded, hipDeviceMallocUncached);
+    const hipError_t e = ek_dev_malloc_flags(ptr, rounded, hipDeviceMallocUncached);
     if (e == hipSuccess)
         g_uc_live.push_back({device, *ptr, rounded});
     return e;
@@ -209,8 +209,8 @@ bool ek_poison()
 hipError_t ek_malloc_named(ek_ctx *c, void **ptr, size_t bytes, const char *name)
 {
     if (!ek_poison())
-        return hipMalloc(ptr, bytes);
-    hipError_t e = hipMalloc(ptr, bytes + EK_GUARD_BYTES);
+        return ek_dev_malloc(ptr, bytes);
+    hipError_t e = ek_dev_malloc(ptr, bytes + EK_GUARD_BYTES);
     // (not 0xff: an index of -1 and a NaN distance are what the kernels treat as "nothing
     // there"; 0x5a5a5a5a is a frame number no shard has and 1.5e16 a distance that wins)
     static const int fill = getenv("EK_POISON_BYTE") ? (int)strtol(getenv("EK_POISON_BYTE"), nullptr, 0)
@@ -259,9 +259,11 @@ int ek_spec_alloc(ek_ctx *c)
     if (!c->pm) {
         const size_t nb = ((size_t)std::max<int64_t>(c->n, 1) + EK_BLOCK - 1) /
                           EK_BLOCK;
+        // (fm first: pm is what says that both are there)
+        if (!c->fm)
+            EK_HIP(ek_malloc_named(c, (void **)&c->fm, 4 * nb * sizeof(EkBlockMax), "fm"));
         EK_HIP(ek_malloc_named(c, (void **)&c->pm,
                                (size_t)(EK_MAX_CANDS - 1) * nb * sizeof(EkBlockMax), "pm"));
-        EK_HIP(ek_malloc_named(c, (void **)&c->fm, 4 * nb * sizeof(EkBlockMax), "fm"));
     }
     if (!c->vecs) {
         const size_t bytes = (size_t)(EK_MAX_CANDS - 1) * std::max<int64_t>(c->n_pad, 1) *
@@ -292,113 +294,113 @@ int ek_free_all(ek_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->tiles);
-    (void)hipFree(c->qtiles);
-    (void)hipFree(c->aos);
-    (void)hipFree(c->G);
-    (void)hipFree(c->dist);
-    (void)hipFree(c->assign);
-    (void)hipFree(c->scratch);
-    (void)hipFree(c->rec);
-    (void)hipFree(c->rec_tmp);
-    (void)hipFree(c->blockmax);
-    (void)hipFree(c->hist);
-    (void)hipFree(c->ctl);
+    (void)ek_dev_free(c->tiles);
+    (void)ek_dev_free(c->qtiles);
+    (void)ek_dev_free(c->aos);
+    (void)ek_dev_free(c->G);
+    (void)ek_dev_free(c->dist);
+    (void)ek_dev_free(c->assign);
+    (void)ek_dev_free(c->scratch);
+    (void)ek_dev_free(c->rec);
+    (void)ek_dev_free(c->rec_tmp);
+    (void)ek_dev_free(c->blockmax);
+    (void)ek_dev_free(c->hist);
+    (void)ek_dev_free(c->ctl);
     for (int b = 0; b < 2; ++b) {
-        (void)hipFree(c->stage[b]);
-        (void)hipHostFree(c->pin[b]);
+        (void)ek_dev_free(c->stage[b]);
+        (void)ek_pinned_free(c->pin[b]);
         if (c->up_ev[b])
-            (void)hipEventDestroy(c->up_ev[b]);
+            (void)ek_event_destroy(c->up_ev[b]);
     }
     delete c->pool;
-    (void)hipFree(c->cen_aos);
-    (void)hipFree(c->cen_G);
-    (void)hipFree(c->cen_tiles);
-    (void)hipFree(c->cen_blocks);
-    (void)hipFree(c->bat_blockcnt);
-    (void)hipFree(c->bat_scan);
-    (void)hipFree(c->bat_sel);
-    (void)hipFree(c->pam_vecs);
-    (void)hipFree(c->pam_recs);
-    (void)hipFree(c->pam_plan);
-    (void)hipFree(c->moved);
-    (void)hipFree(c->tmp_idx);
-    (void)hipFree(c->pam_out_dev);
-    (void)hipFree(c->med_list);
-    (void)hipFree(c->dtab);
+    (void)ek_dev_free(c->cen_aos);
+    (void)ek_dev_free(c->cen_G);
+    (void)ek_dev_free(c->cen_tiles);
+    (void)ek_dev_free(c->cen_blocks);
+    (void)ek_dev_free(c->bat_blockcnt);
+    (void)ek_dev_free(c->bat_scan);
+    (void)ek_dev_free(c->bat_sel);
+    (void)ek_dev_free(c->pam_vecs);
+    (void)ek_dev_free(c->pam_recs);
+    (void)ek_dev_free(c->pam_plan);
+    (void)ek_dev_free(c->moved);
+    (void)ek_dev_free(c->tmp_idx);
+    (void)ek_dev_free(c->pam_out_dev);
+    (void)ek_dev_free(c->med_list);
+    (void)ek_dev_free(c->dtab);
     if (c->act_n_host)
-        (void)hipHostFree(c->act_n_host);
+        (void)ek_pinned_free(c->act_n_host);
     if (c->pam_out_host)
-        (void)hipHostFree(c->pam_out_host);
-    (void)hipFree(c->pam_win_dev);
-    (void)hipFree(c->sp_buf);
-    (void)hipFree(c->act_list);
+        (void)ek_pinned_free(c->pam_out_host);
+    (void)ek_dev_free(c->pam_win_dev);
+    (void)ek_dev_free(c->sp_buf);
+    (void)ek_dev_free(c->act_list);
     if (c->pam_win_host)
-        (void)hipHostFree(c->pam_win_host);
+        (void)ek_pinned_free(c->pam_win_host);
     ek_msm_scratch_free(c->msm_scratch);
     for (void *m : c->ms_ipc)
         (void)hipIpcCloseMemHandle(m);
-    (void)hipFree(c->ms);
+    (void)ek_dev_free(c->ms);
     ek_uncached_free(c->device, c->ms_mbox);
     ek_uncached_free(c->device, c->ms_flags);
-    (void)hipFree(c->recsT);
-    (void)hipFree(c->ctile);
-    (void)hipFree(c->ctrace);
-    (void)hipFree(c->ti_D);
-    (void)hipFree(c->ti_tab);
-    (void)hipFree(c->ti_tabG);
-    (void)hipFree(c->ti_skip);
-    (void)hipFree(c->ti_stats);
-    (void)hipFree(c->pend);
-    (void)hipFree(c->ord);
-    (void)hipFree(c->tick);
-    (void)hipFree(c->rows);
-    (void)hipFree(c->vmask);
-    (void)hipFree(c->plan);
-    (void)hipFree(c->vecs);
-    (void)hipFree(c->hdr);
-    (void)hipFree(c->pm);
-    (void)hipFree(c->ti_rtab);
-    (void)hipFree(c->ti_tmask);
-    (void)hipFree(c->pam_dprop);
-    (void)hipHostFree(c->sel_host);
-    (void)hipHostFree(c->cnt_host);
-    (void)hipHostFree(c->js_host);
-    (void)hipFree(c->sp_marks);
+    (void)ek_dev_free(c->recsT);
+    (void)ek_dev_free(c->ctile);
+    (void)ek_dev_free(c->ctrace);
+    (void)ek_dev_free(c->ti_D);
+    (void)ek_dev_free(c->ti_tab);
+    (void)ek_dev_free(c->ti_tabG);
+    (void)ek_dev_free(c->ti_skip);
+    (void)ek_dev_free(c->ti_stats);
+    (void)ek_dev_free(c->pend);
+    (void)ek_dev_free(c->ord);
+    (void)ek_dev_free(c->tick);
+    (void)ek_dev_free(c->rows);
+    (void)ek_dev_free(c->vmask);
+    (void)ek_dev_free(c->plan);
+    (void)ek_dev_free(c->vecs);
+    (void)ek_dev_free(c->hdr);
+    (void)ek_dev_free(c->pm);
+    (void)ek_dev_free(c->ti_rtab);
+    (void)ek_dev_free(c->ti_tmask);
+    (void)ek_dev_free(c->pam_dprop);
+    (void)ek_pinned_free(c->sel_host);
+    (void)ek_pinned_free(c->cnt_host);
+    (void)ek_pinned_free(c->js_host);
+    (void)ek_dev_free(c->sp_marks);
     if (c->win_ev)
-        (void)hipEventDestroy(c->win_ev);
-    (void)hipFree(c->fm);
+        (void)ek_event_destroy(c->win_ev);
+    (void)ek_dev_free(c->fm);
     ek_view_free(c);
-    (void)hipFree(c->top);
-    (void)hipFree(c->planD);
-    (void)hipFree(c->ndist);
-    (void)hipFree(c->nassign);
-    (void)hipFree(c->amb);
-    (void)hipFree(c->amb_best);
-    (void)hipFree(c->amb_count);
-    (void)hipFree(c->blockcnt);
-    (void)hipFree(c->scan);
-    (void)hipFree(c->sel);
-    (void)hipFree(c->sq_part);
-    (void)hipFree(c->pw_shapes);
-    (void)hipFree(c->sq_out);
-    (void)hipFree(c->med_aos);
-    (void)hipFree(c->med_G);
-    (void)hipFree(c->med_idx);
-    (void)hipFree(c->ambt);
-    (void)hipFree(c->ambG);
+    (void)ek_dev_free(c->top);
+    (void)ek_dev_free(c->planD);
+    (void)ek_dev_free(c->ndist);
+    (void)ek_dev_free(c->nassign);
+    (void)ek_dev_free(c->amb);
+    (void)ek_dev_free(c->amb_best);
+    (void)ek_dev_free(c->amb_count);
+    (void)ek_dev_free(c->blockcnt);
+    (void)ek_dev_free(c->scan);
+    (void)ek_dev_free(c->sel);
+    (void)ek_dev_free(c->sq_part);
+    (void)ek_dev_free(c->pw_shapes);
+    (void)ek_dev_free(c->sq_out);
+    (void)ek_dev_free(c->med_aos);
+    (void)ek_dev_free(c->med_G);
+    (void)ek_dev_free(c->med_idx);
+    (void)ek_dev_free(c->ambt);
+    (void)ek_dev_free(c->ambG);
     for (hipEvent_t e : c->samp_ev)
-        (void)hipEventDestroy(e);
+        (void)ek_event_destroy(e);
     if (c->ev0)
-        (void)hipEventDestroy(c->ev0);
+        (void)ek_event_destroy(c->ev0);
     if (c->ev1)
-        (void)hipEventDestroy(c->ev1);
+        (void)ek_event_destroy(c->ev1);
     if (c->evb0)
-        (void)hipEventDestroy(c->evb0);
+        (void)ek_event_destroy(c->evb0);
     if (c->evb1)
-        (void)hipEventDestroy(c->evb1);
+        (void)ek_event_destroy(c->evb1);
     if (c->own_stream && c->stream)
-        (void)hipStreamDestroy(c->stream);
+        (void)ek_stream_destroy(c->stream);
     delete c;
     return EK_OK;
 }
@@ -427,10 +429,10 @@ extern "C" int ek_ctx_create(int device, int64_t n_frames, int32_t n_atoms,
     if (stream) {
         c->stream = (hipStream_t)stream;
     } else {
-        hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+        hipError_t e = ek_stream_create_flags(&c->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
             delete c;
-            return ek_fail(EK_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
+            return ek_fail(EK_EHIP, "ek_ctx_create: creating the stream: %s", hipGetErrorString(e));
         }
         c->own_stream = true;
     }
@@ -473,9 +475,9 @@ extern "C" int ek_ctx_create(int device, int64_t n_frames, int32_t n_atoms,
 #undef EK_ALLOC
     c->n_pad = (int64_t)nt * EK_TILE;
     if (e == hipSuccess)
-        e = hipEventCreate(&c->ev0);
+        e = ek_event_create(&c->ev0);
     if (e == hipSuccess)
-        e = hipEventCreate(&c->ev1);
+        e = ek_event_create(&c->ev1);
     if (e == hipSuccess && c->n_tiles > 0)  // zero the (padded) last tile
         e = hipMemsetAsync(c->tiles + (size_t)(c->n_tiles - 1) * tile_floats, 0,
                            tile_floats * sizeof(float), c->stream);
@@ -753,18 +755,18 @@ extern "C" int ek_load_frames(ek_ctx *c, const float *xyz, int64_t first,
         if (chunk > c->stage_frames) {      // (the buffers only grow)
             EK_HIP(hipStreamSynchronize(c->stream));
             for (int b = 0; b < 2; ++b) {
-                (void)hipFree(c->stage[b]);
-                (void)hipHostFree(c->pin[b]);
+                (void)ek_dev_free(c->stage[b]);
+                (void)ek_pinned_free(c->pin[b]);
                 c->stage[b] = c->pin[b] = nullptr;
                 c->up_busy[b] = false;
             }
             c->stage_frames = 0;
             const size_t bytes = (size_t)chunk * frame_floats * sizeof(float);
             for (int b = 0; b < 2; ++b) {
-                EK_HIP(hipMalloc((void **)&c->stage[b], bytes));
-                EK_HIP(hipHostMalloc((void **)&c->pin[b], bytes, hipHostMallocDefault));
+                EK_HIP(ek_dev_malloc((void **)&c->stage[b], bytes));
+                EK_HIP(ek_pinned_malloc((void **)&c->pin[b], bytes, hipHostMallocDefault));
                 if (!c->up_ev[b])
-                    EK_HIP(hipEventCreateWithFlags(&c->up_ev[b], hipEventDisableTiming));
+                    EK_HIP(ek_event_create_flags(&c->up_ev[b], hipEventDisableTiming));
             }
             c->stage_frames = chunk;
         }
@@ -826,15 +828,15 @@ int ek_upload_centers(ek_ctx *c, const float *xyz, int32_t K)
     const size_t frame_floats = (size_t)3 * c->A;
     if (K > c->cen_cap) {
         EK_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->cen_aos);
-        (void)hipFree(c->cen_G);
+        (void)ek_dev_free(c->cen_aos);
+        (void)ek_dev_free(c->cen_G);
         c->cen_aos = nullptr;
         c->cen_G = nullptr;
         c->cen_cap = 0;
         // 2 buffers: raw (second half) and centred (first half)
-        EK_HIP(hipMalloc((void **)&c->cen_aos,
+        EK_HIP(ek_dev_malloc((void **)&c->cen_aos,
                          (size_t)2 * K * frame_floats * sizeof(float)));
-        EK_HIP(hipMalloc((void **)&c->cen_G, (size_t)K * sizeof(double)));
+        EK_HIP(ek_dev_malloc((void **)&c->cen_G, (size_t)K * sizeof(double)));
         c->cen_cap = K;
     }
     float *raw = c->cen_aos + (size_t)c->cen_cap * frame_floats;
@@ -977,13 +979,22 @@ int ek_ensure_hist(ek_ctx *c, int32_t label)
     int32_t cap = c->hist_cap;
     while (cap <= label)
         cap *= 2;
+    // (h belongs to nobody until the context takes it: every failure gives it back)
     EkHist *h = nullptr;
-    EK_HIP(hipMalloc((void **)&h, (size_t)cap * sizeof(EkHist)));
-    EK_HIP(hipMemsetAsync(h, 0, (size_t)cap * sizeof(EkHist), c->stream));
-    EK_HIP(hipMemcpyAsync(h, c->hist, (size_t)c->hist_cap * sizeof(EkHist),
-                          hipMemcpyDeviceToDevice, c->stream));
-    EK_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->hist);
+    hipError_t e = ek_dev_malloc((void **)&h, (size_t)cap * sizeof(EkHist));
+    if (e == hipSuccess)
+        e = hipMemsetAsync(h, 0, (size_t)cap * sizeof(EkHist), c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(h, c->hist, (size_t)c->hist_cap * sizeof(EkHist),
+                           hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)ek_dev_free(h);
+        EK_HIP(e);
+    }
+    (void)ek_dev_free(c->hist);
     c->hist = h;
     c->hist_cap = cap;
     return EK_OK;
@@ -1025,29 +1036,39 @@ extern "C" int ek_kcenters_step(ek_ctx *c, const void *recs_dev, int32_t n_recs,
                 float *t2 = nullptr, *d2 = nullptr;
                 double *g2 = nullptr;
                 EK_HIP(ek_wait(c));
-                EK_HIP(hipMalloc((void **)&t2, (size_t)cap * 3 * c->A * sizeof(float)));
-                EK_HIP(hipMalloc((void **)&g2, (size_t)cap * sizeof(double)));
-                EK_HIP(hipMalloc((void **)&d2, (size_t)cap * sizeof(float)));
-                if (c->ti_tab_n > 0) {
-                    EK_HIP(hipMemcpy(t2, c->ti_tab, (size_t)c->ti_tab_n * 3 * c->A *
-                                                        sizeof(float),
-                                     hipMemcpyDeviceToDevice));
-                    EK_HIP(hipMemcpy(g2, c->ti_tabG, (size_t)c->ti_tab_n * sizeof(double),
-                                     hipMemcpyDeviceToDevice));
+                // (the three belong to nobody until the context takes them: every
+                // failure gives them back)
+                hipError_t e = ek_dev_malloc((void **)&t2, (size_t)cap * 3 * c->A * sizeof(float));
+                if (e == hipSuccess)
+                    e = ek_dev_malloc((void **)&g2, (size_t)cap * sizeof(double));
+                if (e == hipSuccess)
+                    e = ek_dev_malloc((void **)&d2, (size_t)cap * sizeof(float));
+                if (e == hipSuccess && c->ti_tab_n > 0)
+                    e = hipMemcpy(t2, c->ti_tab, (size_t)c->ti_tab_n * 3 * c->A * sizeof(float),
+                                  hipMemcpyDeviceToDevice);
+                if (e == hipSuccess && c->ti_tab_n > 0)
+                    e = hipMemcpy(g2, c->ti_tabG, (size_t)c->ti_tab_n * sizeof(double),
+                                  hipMemcpyDeviceToDevice);
+                if (e != hipSuccess) {
+                    (void)ek_dev_free(t2);
+                    (void)ek_dev_free(g2);
+                    (void)ek_dev_free(d2);
+                    EK_HIP(e);
                 }
-                (void)hipFree(c->ti_tab);
-                (void)hipFree(c->ti_tabG);
-                (void)hipFree(c->ti_D);
+                (void)ek_dev_free(c->ti_tab);
+                (void)ek_dev_free(c->ti_tabG);
+                (void)ek_dev_free(c->ti_D);
                 c->ti_tab = t2;
                 c->ti_tabG = g2;
                 c->ti_D = d2;
                 c->ti_tab_cap = cap;
                 c->ti_cap = cap;
             }
-            if (!c->ti_skip) {
-                EK_HIP(hipMalloc((void **)&c->ti_skip,
-                                 (size_t)std::max<int64_t>(c->n_tiles, 1)));
-                EK_HIP(hipMalloc((void **)&c->ti_stats, 2 * sizeof(unsigned long long)));
+            if (!c->ti_skip)        // (each only if it is missing)
+                EK_HIP(ek_dev_malloc((void **)&c->ti_skip,
+                                     (size_t)std::max<int64_t>(c->n_tiles, 1)));
+            if (!c->ti_stats) {
+                EK_HIP(ek_dev_malloc((void **)&c->ti_stats, 2 * sizeof(unsigned long long)));
                 EK_HIP(hipMemsetAsync(c->ti_stats, 0, 2 * sizeof(unsigned long long),
                                       c->stream));
             }
@@ -1129,7 +1150,7 @@ extern "C" int ek_timing_begin(ek_ctx *c, int32_t sample_every,
     EK_HIP(hipSetDevice(c->device));
     while (c->samp_ev.size() < 2 * (size_t)max_samples) {
         hipEvent_t e;
-        EK_HIP(hipEventCreate(&e));
+        EK_HIP(ek_event_create(&e));
         c->samp_ev.push_back(e);
     }
     c->samp_form.assign((size_t)max_samples, 0);
@@ -1228,10 +1249,10 @@ extern "C" int ek_assign_nearest(ek_ctx *c, const float *centers_xyz,
         const size_t need = ek_cblocks16_bytes(n_centers, c->A);
         if (need > c->cen_blocks_cap) {
             EK_HIP(ek_wait(c));
-            (void)hipFree(c->cen_blocks);
+            (void)ek_dev_free(c->cen_blocks);
             c->cen_blocks = nullptr;
             c->cen_blocks_cap = 0;
-            EK_HIP(hipMalloc((void **)&c->cen_blocks, need));
+            EK_HIP(ek_dev_malloc((void **)&c->cen_blocks, need));
             c->cen_blocks_cap = need;
         }
         ek_launch_cblocks16(c->cen_aos, n_centers, c->A, c->cen_blocks, c->stream);
@@ -1241,10 +1262,10 @@ extern "C" int ek_assign_nearest(ek_ctx *c, const float *centers_xyz,
         const int32_t need = (n_centers + EK_TILE - 1) / EK_TILE * EK_TILE;
         if (need > c->cen_tiles_cap) {
             EK_HIP(ek_wait(c));
-            (void)hipFree(c->cen_tiles);
+            (void)ek_dev_free(c->cen_tiles);
             c->cen_tiles = nullptr;
             c->cen_tiles_cap = 0;
-            EK_HIP(hipMalloc((void **)&c->cen_tiles,
+            EK_HIP(ek_dev_malloc((void **)&c->cen_tiles,
                              (size_t)need * 3 * c->A * sizeof(float)));
             c->cen_tiles_cap = need;
         }
@@ -1312,15 +1333,15 @@ extern "C" int ek_hbm_copy_rate(int device, size_t bytes, double *gbytes_per_s)
     const size_t n = bytes / 16;
     ek_probe_f4 *src = nullptr, *dst = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc((void **)&src, n * 16);
+    hipError_t e = ek_dev_malloc((void **)&src, n * 16);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&dst, n * 16);
+        e = ek_dev_malloc((void **)&dst, n * 16);
     if (e == hipSuccess)
         e = hipMemset(src, 0, n * 16);
     if (e == hipSuccess)
-        e = hipEventCreate(&e0);
+        e = ek_event_create(&e0);
     if (e == hipSuccess)
-        e = hipEventCreate(&e1);
+        e = ek_event_create(&e1);
     float best = 0.f, best_read = 0.f;
     if (e == hipSuccess) {
         const unsigned blocks = (unsigned)((n + EK_BLOCK * 8 - 1) / (EK_BLOCK * 8));
@@ -1349,12 +1370,12 @@ extern "C" int ek_hbm_copy_rate(int device, size_t bytes, double *gbytes_per_s)
                 best_read = ms;
         }
     }
-    (void)hipFree(src);
-    (void)hipFree(dst);
+    (void)ek_dev_free(src);
+    (void)ek_dev_free(dst);
     if (e0)
-        (void)hipEventDestroy(e0);
+        (void)ek_event_destroy(e0);
     if (e1)
-        (void)hipEventDestroy(e1);
+        (void)ek_event_destroy(e1);
     if (e != hipSuccess)
         return ek_fail(EK_EHIP, "ek_hbm_copy_rate: %s", hipGetErrorString(e));
     gbytes_per_s[0] = best > 0.f ? 2.0 * (double)(n * 16) / (best * 1e-3) / 1e9 : 0.0;
@@ -1403,7 +1424,7 @@ extern "C" int ek_qcp_probe(int device, const float *S, const double *Gx, const 
                  off_cur = off_S + mm * 36, off_full = off_cur + mm * 4,
                  off_below = off_full + mm * 4, off_cert = off_below + mm * 4,
                  total = off_cert + mm;
-    EK_HIP(hipMalloc((void **)&buf, total));
+    EK_HIP(ek_dev_malloc((void **)&buf, total));
     hipError_t e = hipMemcpy(buf + off_S, S, mm * 36, hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = hipMemcpy(buf + off_Gx, Gx, mm * 8, hipMemcpyHostToDevice);
@@ -1428,7 +1449,7 @@ extern "C" int ek_qcp_probe(int device, const float *S, const double *Gx, const 
         e = hipMemcpy(below, buf + off_below, mm * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
         e = hipMemcpy(cert, buf + off_cert, mm, hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
+    (void)ek_dev_free(buf);
     if (e != hipSuccess)
         return ek_fail(EK_EHIP, "ek_qcp_probe: %s", hipGetErrorString(e));
     return EK_OK;

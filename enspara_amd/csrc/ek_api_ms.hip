@@ -263,7 +263,7 @@ extern "C" int ek_ms_setup(ek_ctx *c, int32_t world, int32_t rank,
     c->ms_mbox = nullptr;
     c->ms_flags = nullptr;
     if (!c->ms)     // (+ a scratch control block for ek_ms_end's pick)
-        EK_HIP(hipMalloc((void **)&c->ms, 64 + sizeof(EkCtl)));
+        EK_HIP(ek_dev_malloc((void **)&c->ms, 64 + sizeof(EkCtl)));
     EkMsXchg x;
     x.world = world;
     x.rank = rank;
@@ -380,7 +380,7 @@ extern "C" int ek_reserve_centers(ek_ctx *c, int32_t n_centers)
     }
     for (int k = 0; k < 4; ++k)
         if (!c->ms_ev[k])
-            EK_HIP(hipEventCreate(&c->ms_ev[k]));
+            EK_HIP(ek_event_create(&c->ms_ev[k]));
     return EK_OK;
 }
 
@@ -620,7 +620,7 @@ extern "C" int ek_ms_run(ek_ctx *c, int32_t first_label, int32_t max_new,
                           sizeof(EkMsState) - offsetof(EkMsState, n_reoffer), c->stream));
     for (int k = 0; k < 4; ++k)
         if (!c->ms_ev[k])
-            EK_HIP(hipEventCreate(&c->ms_ev[k]));
+            EK_HIP(ek_event_create(&c->ms_ev[k]));
     c->ms_t[0] = c->ms_t[1] = c->ms_t[2] = 0.0;
     c->ms_t_n = 0;
     while (max_new > 0) {

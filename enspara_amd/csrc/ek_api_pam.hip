@@ -7,16 +7,27 @@ static int ek_pam_alloc(ek_ctx *c, int32_t K)
 {
     const size_t nn = (size_t)std::max<int64_t>(c->n, 1);
     const size_t nb = (nn + EK_BLOCK - 1) / EK_BLOCK;
-    if (!c->ndist) {
-        EK_HIP(hipMalloc((void **)&c->ndist, nn * sizeof(float)));
-        EK_HIP(hipMalloc((void **)&c->nassign, nn * sizeof(int32_t)));
-        EK_HIP(hipMalloc((void **)&c->amb, nn * sizeof(uint32_t)));
-        EK_HIP(hipMalloc((void **)&c->amb_best, nn * sizeof(unsigned long long)));
+    c->med_K = 0;       // (no working set until this call is through: the entry points test it)
+    // (tested by its last member, each buffer made only if it is missing: a call that
+    // failed part-way leaves what it got with the context, and the next call makes the rest)
+    if (!c->pam_win_host) {
+        if (!c->ndist)
+            EK_HIP(ek_dev_malloc((void **)&c->ndist, nn * sizeof(float)));
+        if (!c->nassign)
+            EK_HIP(ek_dev_malloc((void **)&c->nassign, nn * sizeof(int32_t)));
+        if (!c->amb)
+            EK_HIP(ek_dev_malloc((void **)&c->amb, nn * sizeof(uint32_t)));
+        if (!c->amb_best)
+            EK_HIP(ek_dev_malloc((void **)&c->amb_best, nn * sizeof(unsigned long long)));
         // [0] ambiguous members, [1] their reach (float bits), [2] listed medoids
-        EK_HIP(hipMalloc((void **)&c->amb_count, 4 * sizeof(unsigned int)));
-        EK_HIP(hipMalloc((void **)&c->blockcnt, nb * sizeof(int32_t)));
-        EK_HIP(hipMalloc((void **)&c->scan, nb * sizeof(int64_t)));
-        EK_HIP(hipMalloc((void **)&c->sel, 2 * sizeof(int64_t)));
+        if (!c->amb_count)
+            EK_HIP(ek_dev_malloc((void **)&c->amb_count, 4 * sizeof(unsigned int)));
+        if (!c->blockcnt)
+            EK_HIP(ek_dev_malloc((void **)&c->blockcnt, nb * sizeof(int32_t)));
+        if (!c->scan)
+            EK_HIP(ek_dev_malloc((void **)&c->scan, nb * sizeof(int64_t)));
+        if (!c->sel)
+            EK_HIP(ek_dev_malloc((void **)&c->sel, 2 * sizeof(int64_t)));
         {
             EkPwShape hs[2];
             const int64_t n_full = c->n / EK_PW_CHUNK;
@@ -47,29 +58,40 @@ static int ek_pam_alloc(ek_ctx *c, int32_t K)
             c->pw_n_full = (int)n_full;
             c->pw_leaves = (int)n_full * EK_PW_FULL_LEAVES + hs[1].n_leaves;
             c->pw_chunks = (int)n_full + (last_len > 0 ? 1 : 0);
-            EK_HIP(hipMalloc((void **)&c->pw_shapes, sizeof(hs)));
+            if (!c->pw_shapes)
+                EK_HIP(ek_dev_malloc((void **)&c->pw_shapes, sizeof(hs)));
             EK_HIP(hipMemcpy(c->pw_shapes, hs, sizeof(hs), hipMemcpyHostToDevice));
-            EK_HIP(hipMalloc((void **)&c->sq_part,
+            if (!c->sq_part)
+                EK_HIP(ek_dev_malloc((void **)&c->sq_part,
                              (2 * (size_t)std::max(c->pw_leaves, 1) +
                               2 * (size_t)std::max(c->pw_chunks, 1)) *
                                  sizeof(double)));
         }
-        EK_HIP(hipMalloc((void **)&c->sq_out, 2 * sizeof(double)));
-        EK_HIP(hipMalloc((void **)&c->bat_blockcnt,
+        if (!c->sq_out)
+            EK_HIP(ek_dev_malloc((void **)&c->sq_out, 2 * sizeof(double)));
+        if (!c->bat_blockcnt)
+            EK_HIP(ek_dev_malloc((void **)&c->bat_blockcnt,
                          (size_t)EK_PAM_WIN * nb * sizeof(int32_t)));
-        EK_HIP(hipMalloc((void **)&c->bat_scan,
+        if (!c->bat_scan)
+            EK_HIP(ek_dev_malloc((void **)&c->bat_scan,
                          (size_t)EK_PAM_WIN * nb * sizeof(int64_t)));
         // [0,8) counts, [8,16) selected frames, [16,24) requested member ranks
-        EK_HIP(hipMalloc((void **)&c->bat_sel,
+        if (!c->bat_sel)
+            EK_HIP(ek_dev_malloc((void **)&c->bat_sel,
                          3 * EK_PAM_WIN * sizeof(int64_t)));
-        EK_HIP(hipMalloc((void **)&c->moved, sizeof(unsigned int)));
+        if (!c->moved)
+            EK_HIP(ek_dev_malloc((void **)&c->moved, sizeof(unsigned int)));
         EK_HIP(hipMemsetAsync(c->moved, 0, sizeof(unsigned int), c->stream));
-        EK_HIP(hipMalloc((void **)&c->pam_out_dev, sizeof(EkPamOut)));
-        EK_HIP(hipHostMalloc((void **)&c->pam_out_host, sizeof(EkPamOut),
+        if (!c->pam_out_dev)
+            EK_HIP(ek_dev_malloc((void **)&c->pam_out_dev, sizeof(EkPamOut)));
+        if (!c->pam_out_host)
+            EK_HIP(ek_pinned_malloc((void **)&c->pam_out_host, sizeof(EkPamOut),
                              hipHostMallocDefault));
-        EK_HIP(hipMalloc((void **)&c->pam_win_dev, sizeof(EkPamWin)));
+        if (!c->pam_win_dev)
+            EK_HIP(ek_dev_malloc((void **)&c->pam_win_dev, sizeof(EkPamWin)));
         // (coherent and mapped: the window's kernel writes the record there itself)
-        EK_HIP(hipHostMalloc((void **)&c->pam_win_host, sizeof(EkPamWin),
+        if (!c->pam_win_host)
+            EK_HIP(ek_pinned_malloc((void **)&c->pam_win_host, sizeof(EkPamWin),
                              hipHostMallocCoherent | hipHostMallocMapped));
     }
     c->pam_restore = -1;
@@ -83,23 +105,23 @@ static int ek_pam_alloc(ek_ctx *c, int32_t K)
     c->pf_external = false;
     if (K > c->med_cap) {
         EK_HIP(ek_wait(c));
-        (void)hipFree(c->med_aos);
-        (void)hipFree(c->med_G);
-        (void)hipFree(c->med_idx);
-        (void)hipFree(c->med_list);
-        (void)hipFree(c->dtab);
+        (void)ek_dev_free(c->med_aos);
+        (void)ek_dev_free(c->med_G);
+        (void)ek_dev_free(c->med_idx);
+        (void)ek_dev_free(c->med_list);
+        (void)ek_dev_free(c->dtab);
         c->med_list = nullptr;
         c->dtab = nullptr;
         c->med_aos = nullptr;
         c->med_G = nullptr;
         c->med_idx = nullptr;
         c->med_cap = 0;
-        EK_HIP(hipMalloc((void **)&c->med_aos,
+        EK_HIP(ek_dev_malloc((void **)&c->med_aos,
                          (size_t)(K + 1) * 3 * c->A * sizeof(float)));
-        EK_HIP(hipMalloc((void **)&c->med_G, (size_t)(K + 1) * sizeof(double)));
-        EK_HIP(hipMalloc((void **)&c->med_idx, (size_t)(K + 1) * sizeof(int64_t)));
-        EK_HIP(hipMalloc((void **)&c->med_list, (size_t)(K + 1) * sizeof(int32_t)));
-        EK_HIP(hipMalloc((void **)&c->dtab,
+        EK_HIP(ek_dev_malloc((void **)&c->med_G, (size_t)(K + 1) * sizeof(double)));
+        EK_HIP(ek_dev_malloc((void **)&c->med_idx, (size_t)(K + 1) * sizeof(int64_t)));
+        EK_HIP(ek_dev_malloc((void **)&c->med_list, (size_t)(K + 1) * sizeof(int32_t)));
+        EK_HIP(ek_dev_malloc((void **)&c->dtab,
                          (size_t)3 * EK_PAM_WIN * (K + 1) * sizeof(float)));
         c->med_cap = K;
     }
@@ -115,11 +137,11 @@ static int ek_tmp_idx(ek_ctx *c, int64_t count)
     if (count <= c->tmp_idx_cap)
         return EK_OK;
     EK_HIP(ek_wait(c));
-    (void)hipFree(c->tmp_idx);
+    (void)ek_dev_free(c->tmp_idx);
     c->tmp_idx = nullptr;
     c->tmp_idx_cap = 0;
     const int64_t cap = std::max<int64_t>(1024, count);
-    EK_HIP(hipMalloc((void **)&c->tmp_idx, (size_t)cap * sizeof(int64_t)));
+    EK_HIP(ek_dev_malloc((void **)&c->tmp_idx, (size_t)cap * sizeof(int64_t)));
     c->tmp_idx_cap = cap;
     return EK_OK;
 }
@@ -204,7 +226,7 @@ extern "C" int ek_pam_count_members(ek_ctx *c, int32_t cid, int64_t *count)
 {
     if (!c || !count)
         return ek_fail(EK_EARG, "ek_pam_count_members: NULL argument");
-    if (!c->ndist)
+    if (!c->ndist || c->med_K < 1)
         return ek_fail(EK_ESTATE, "ek_pam_count_members: call ek_pam_begin first");
     EK_HIP(hipSetDevice(c->device));
     ek_launch_count_members(c->assign, c->n, cid, c->blockcnt, c->scan, c->sel,
@@ -223,7 +245,7 @@ extern "C" int ek_pam_select_member(ek_ctx *c, int32_t cid, int64_t j,
 {
     if (!c || !frame_index)
         return ek_fail(EK_EARG, "ek_pam_select_member: NULL argument");
-    if (!c->ndist)
+    if (!c->ndist || c->med_K < 1)
         return ek_fail(EK_ESTATE, "ek_pam_select_member: call ek_pam_begin first");
     EK_HIP(hipSetDevice(c->device));
     // relies on the scan left by the preceding ek_pam_count_members(cid)
@@ -321,15 +343,15 @@ static int ek_pam_amb_room(ek_ctx *c, int64_t max_amb)
     if (max_amb <= c->ambt_cap)
         return EK_OK;
     EK_HIP(ek_wait(c));
-    (void)hipFree(c->ambt);
-    (void)hipFree(c->ambG);
+    (void)ek_dev_free(c->ambt);
+    (void)ek_dev_free(c->ambG);
     c->ambt = nullptr;
     c->ambG = nullptr;
     c->ambt_cap = 0;
     const int64_t cap = std::max<int64_t>(
         4096, (max_amb * 5 / 4 + EK_BLOCK - 1) / EK_BLOCK * EK_BLOCK);
-    EK_HIP(hipMalloc((void **)&c->ambt, (size_t)cap * 3 * c->A * sizeof(float)));
-    EK_HIP(hipMalloc((void **)&c->ambG, (size_t)cap * sizeof(double)));
+    EK_HIP(ek_dev_malloc((void **)&c->ambt, (size_t)cap * 3 * c->A * sizeof(float)));
+    EK_HIP(ek_dev_malloc((void **)&c->ambG, (size_t)cap * sizeof(double)));
     c->ambt_cap = cap;
     return EK_OK;
 }
@@ -567,14 +589,18 @@ extern "C" int ek_pam_select_members_batch(ek_ctx *c, int32_t cid0, int32_t coun
 
 static int ek_pam_vecs_alloc(ek_ctx *c)
 {
-    if (!c->pam_vecs) {
-        EK_HIP(hipMalloc((void **)&c->pam_vecs,
+    if (!c->pam_dprop) {     // (as in ek_pam_alloc: by the last, each only if missing)
+        if (!c->pam_vecs)
+            EK_HIP(ek_dev_malloc((void **)&c->pam_vecs,
                          (size_t)EK_PAM_WIN * std::max<int64_t>(c->n_pad, 1) *
                              sizeof(float)));
-        EK_HIP(hipMalloc((void **)&c->pam_recs,
+        if (!c->pam_recs)
+            EK_HIP(ek_dev_malloc((void **)&c->pam_recs,
                          (size_t)EK_PAM_WIN * ek_rec_bytes(c->A)));
-        EK_HIP(hipMalloc((void **)&c->pam_plan, sizeof(EkPlan)));
-        EK_HIP(hipMalloc((void **)&c->pam_dprop, EK_PAM_WIN * sizeof(float)));
+        if (!c->pam_plan)
+            EK_HIP(ek_dev_malloc((void **)&c->pam_plan, sizeof(EkPlan)));
+        if (!c->pam_dprop)
+            EK_HIP(ek_dev_malloc((void **)&c->pam_dprop, EK_PAM_WIN * sizeof(float)));
     }
     return EK_OK;
 }
@@ -602,7 +628,7 @@ static int ek_pam_prefetch_vectors(ek_ctx *c, int count, int32_t win_lo,
     else if (c->prune && c->state_exact && c->A >= 3 && win_count > 0 &&
              c->n >= 16384) {
         if (!c->act_n_host)
-            EK_HIP(hipHostMalloc((void **)&c->act_n_host, sizeof(unsigned int),
+            EK_HIP(ek_pinned_malloc((void **)&c->act_n_host, sizeof(unsigned int),
                                  hipHostMallocDefault));
         // O (old medoids of the window's clusters) only where the window's slots
         // and the proposals coincide: ek_pam_window_run's pruning reads it
@@ -620,7 +646,7 @@ static int ek_pam_prefetch_vectors(ek_ctx *c, int count, int32_t win_lo,
         if (c->pam_bounds_off > 0)
             --c->pam_bounds_off;
         if (!c->act_list)
-            EK_HIP(hipMalloc((void **)&c->act_list,
+            EK_HIP(ek_dev_malloc((void **)&c->act_list,
                              (size_t)std::max<int64_t>(c->n, 1) * sizeof(uint32_t)));
         // the vectors go back to +inf: the entries the window before wrote, if
         // that is all there is (before the list is overwritten)
@@ -770,7 +796,7 @@ static int ek_pam_select_prefetch(ek_ctx *c, int32_t cid0, int32_t count,
     if (rc)
         return rc;
     if (!c->sel_host)
-        EK_HIP(hipHostMalloc((void **)&c->sel_host, EK_PAM_WIN * sizeof(int64_t),
+        EK_HIP(ek_pinned_malloc((void **)&c->sel_host, EK_PAM_WIN * sizeof(int64_t),
                              hipHostMallocCoherent | hipHostMallocMapped));
     // (the drawn ranks are read by the selection from mapped host memory, the selected
     // frames written into it: no copy either way)
@@ -778,7 +804,7 @@ static int ek_pam_select_prefetch(ek_ctx *c, int32_t cid0, int32_t count,
     const int64_t *js_dev_view = nullptr;
     if (c->pam_zero_copy) {
         if (!c->js_host)
-            EK_HIP(hipHostMalloc((void **)&c->js_host, EK_PAM_WIN * sizeof(int64_t),
+            EK_HIP(ek_pinned_malloc((void **)&c->js_host, EK_PAM_WIN * sizeof(int64_t),
                                  hipHostMallocCoherent | hipHostMallocMapped));
         void *dp = nullptr, *dj = nullptr;
         if (hipHostGetDevicePointer(&dp, c->sel_host, 0) == hipSuccess &&
@@ -840,11 +866,11 @@ static int ek_pam_window_sparse(ek_ctx *c, int32_t cid0, int32_t count,
     const size_t o_bcnt = o_bucket + (size_t)EK_PAM_WIN * cap * sizeof(uint2);
     const size_t o_spec = o_bcnt + 256;
     if (!c->sp_buf) {
-        EK_HIP(hipMalloc((void **)&c->sp_buf, o_spec + ek_sp_spec_bytes()));
+        EK_HIP(ek_dev_malloc((void **)&c->sp_buf, o_spec + ek_sp_spec_bytes()));
         c->sp_bcnt_clean = false;
     }
     if (c->pam_spec && !c->sp_marks) {
-        EK_HIP(hipMalloc((void **)&c->sp_marks, (size_t)c->n * sizeof(unsigned long long)));
+        EK_HIP(ek_dev_malloc((void **)&c->sp_marks, (size_t)c->n * sizeof(unsigned long long)));
         EK_HIP(hipMemsetAsync(c->sp_marks, 0, (size_t)c->n * sizeof(unsigned long long),
                               c->stream));
     }
@@ -920,7 +946,7 @@ static int ek_pam_window_sparse(ek_ctx *c, int32_t cid0, int32_t count,
     static unsigned long long prof_tot[16];
     static int prof_n = 0;
     if (!prof_dev) {
-        EK_HIP(hipMalloc((void **)&prof_dev, 16 * sizeof(unsigned long long)));
+        EK_HIP(ek_dev_malloc((void **)&prof_dev, 16 * sizeof(unsigned long long)));
         EK_HIP(hipMemset(prof_dev, 0, 16 * sizeof(unsigned long long)));
     }
     a.prof = prof_dev;
@@ -1078,7 +1104,7 @@ static int ek_pam_window_run_impl(ek_ctx *c, int32_t cid0, int32_t count,
     if (next_count > 0) {
         if (c->pam_zero_copy) {
             if (!c->cnt_host)
-                EK_HIP(hipHostMalloc((void **)&c->cnt_host, EK_PAM_WIN * sizeof(int64_t),
+                EK_HIP(ek_pinned_malloc((void **)&c->cnt_host, EK_PAM_WIN * sizeof(int64_t),
                                      hipHostMallocCoherent | hipHostMallocMapped));
             void *dp = nullptr;
             if (hipHostGetDevicePointer(&dp, c->cnt_host, 0) == hipSuccess)
@@ -1099,7 +1125,7 @@ static int ek_pam_window_run_impl(ek_ctx *c, int32_t cid0, int32_t count,
         // the accepted proposals' rows of the medoid table and the slots' marks: behind
         // what the host waits for
         if (!c->win_ev)
-            EK_HIP(hipEventCreateWithFlags(&c->win_ev, hipEventDisableTiming));
+            EK_HIP(ek_event_create_flags(&c->win_ev, hipEventDisableTiming));
         EK_HIP(hipEventRecord(c->win_ev, c->stream));
         ek_launch_sp_finish(sp_args, c->stream);
         EK_CHECK_LAUNCH();

@@ -10,16 +10,16 @@
 // ---- the active view's buffers (kernels: ek_view.hip; when to build one: EkViewPolicy) -------
 void ek_view_free(ek_ctx *c)
 {
-    (void)hipFree(c->v_aos);
-    (void)hipFree(c->v_tiles);
-    (void)hipFree(c->v_qtiles);
-    (void)hipFree(c->v_G);
-    (void)hipFree(c->v_dist);
-    (void)hipFree(c->v_assign);
-    (void)hipFree(c->v_act);
-    (void)hipFree(c->v_blockcnt);
-    (void)hipFree(c->v_blockoff);
-    (void)hipFree(c->v_count);
+    (void)ek_dev_free(c->v_aos);
+    (void)ek_dev_free(c->v_tiles);
+    (void)ek_dev_free(c->v_qtiles);
+    (void)ek_dev_free(c->v_G);
+    (void)ek_dev_free(c->v_dist);
+    (void)ek_dev_free(c->v_assign);
+    (void)ek_dev_free(c->v_act);
+    (void)ek_dev_free(c->v_blockcnt);
+    (void)ek_dev_free(c->v_blockoff);
+    (void)ek_dev_free(c->v_count);
     c->v_aos = c->v_tiles = c->v_qtiles = nullptr;
     c->v_G = nullptr;
     c->v_dist = nullptr;
@@ -202,30 +202,30 @@ static int ek_run_reserve_tri(ek_ctx *c, int32_t goal)
 {
     if (goal > c->ti_cap) {
         EK_HIP(ek_wait(c));
-        (void)hipFree(c->ti_D);
+        (void)ek_dev_free(c->ti_D);
         c->ti_D = nullptr;
         c->ti_cap = 0;
-        EK_HIP(hipMalloc((void **)&c->ti_D, (size_t)(goal + 1) * sizeof(float)));
+        EK_HIP(ek_dev_malloc((void **)&c->ti_D, (size_t)(goal + 1) * sizeof(float)));
         c->ti_cap = goal + 1;
     }
-    if (!c->ti_skip) {
-        EK_HIP(hipMalloc((void **)&c->ti_skip,
-                         (size_t)std::max<int64_t>(c->n_tiles, 1)));
-        EK_HIP(hipMalloc((void **)&c->ti_stats, 2 * sizeof(unsigned long long)));
-    }
+    if (!c->ti_skip)        // (each only if it is missing)
+        EK_HIP(ek_dev_malloc((void **)&c->ti_skip,
+                             (size_t)std::max<int64_t>(c->n_tiles, 1)));
+    if (!c->ti_stats)
+        EK_HIP(ek_dev_malloc((void **)&c->ti_stats, 2 * sizeof(unsigned long long)));
     EK_HIP(hipMemsetAsync(c->ti_stats, 0, 2 * sizeof(unsigned long long),
                           c->stream));
     if (goal > c->ti_rtab_cap) {
         EK_HIP(ek_wait(c));
-        (void)hipFree(c->ti_rtab);
+        (void)ek_dev_free(c->ti_rtab);
         c->ti_rtab = nullptr;
         c->ti_rtab_cap = 0;
-        EK_HIP(hipMalloc((void **)&c->ti_rtab,
+        EK_HIP(ek_dev_malloc((void **)&c->ti_rtab,
                          (size_t)(goal + 1) * EK_MAX_CANDS * sizeof(float)));
         c->ti_rtab_cap = goal + 1;
     }
     if (!c->ti_tmask)
-        EK_HIP(hipMalloc((void **)&c->ti_tmask,
+        EK_HIP(ek_dev_malloc((void **)&c->ti_tmask,
                          (size_t)std::max<int64_t>(c->n_tiles, 1) * sizeof(uint32_t)));
     return EK_OK;
 }
@@ -614,8 +614,8 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
 {
     EK_RC(ek_spec_alloc(c));
     if (!c->evb0) {
-        EK_HIP(hipEventCreate(&c->evb0));
-        EK_HIP(hipEventCreate(&c->evb1));
+        EK_HIP(ek_event_create(&c->evb0));
+        EK_HIP(ek_event_create(&c->evb1));
     }
     const int32_t goal = first_label + max_new;
     EkCtl ctlw;
@@ -848,19 +848,19 @@ extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
     double *r_G = nullptr;
     int32_t *r_assign = nullptr;
     unsigned long long *diff = nullptr, got[3] = {0, 0, 0};
-    hipError_t e = hipMalloc((void **)&r_aos, (size_t)nv * A3 * sizeof(float));
+    hipError_t e = ek_dev_malloc((void **)&r_aos, (size_t)nv * A3 * sizeof(float));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&r_tiles, tile_words * sizeof(float));
+        e = ek_dev_malloc((void **)&r_tiles, tile_words * sizeof(float));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&r_qtiles, quad_bytes);
+        e = ek_dev_malloc((void **)&r_qtiles, quad_bytes);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&r_G, (size_t)nv * sizeof(double));
+        e = ek_dev_malloc((void **)&r_G, (size_t)nv * sizeof(double));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&r_dist, (size_t)nv * sizeof(float));
+        e = ek_dev_malloc((void **)&r_dist, (size_t)nv * sizeof(float));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&r_assign, (size_t)nv * sizeof(int32_t));
+        e = ek_dev_malloc((void **)&r_assign, (size_t)nv * sizeof(int32_t));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&diff, sizeof(got));
+        e = ek_dev_malloc((void **)&diff, sizeof(got));
     if (e == hipSuccess)
         e = hipMemsetAsync(diff, 0, sizeof(got), c->stream);
     if (e == hipSuccess)
@@ -887,13 +887,13 @@ extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
         e = ek_wait(c);
     else
         (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(r_aos);
-    (void)hipFree(r_tiles);
-    (void)hipFree(r_qtiles);
-    (void)hipFree(r_G);
-    (void)hipFree(r_dist);
-    (void)hipFree(r_assign);
-    (void)hipFree(diff);
+    (void)ek_dev_free(r_aos);
+    (void)ek_dev_free(r_tiles);
+    (void)ek_dev_free(r_qtiles);
+    (void)ek_dev_free(r_G);
+    (void)ek_dev_free(r_dist);
+    (void)ek_dev_free(r_assign);
+    (void)ek_dev_free(diff);
     EK_HIP(e);
     out[1] = (int64_t)got[0];
     out[2] = (int64_t)got[1];

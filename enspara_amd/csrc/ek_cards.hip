@@ -345,11 +345,11 @@ static int cd_bind(ek_cards *h, const char *who)
 
 static void cd_free_traj(cd_traj &t)
 {
-    (void)hipFree(t.S);
-    (void)hipFree(t.D);
-    (void)hipFree(t.part);
-    (void)hipFree(t.carry);
-    (void)hipFree(t.stats);
+    (void)ek_dev_free(t.S);
+    (void)ek_dev_free(t.D);
+    (void)ek_dev_free(t.part);
+    (void)ek_dev_free(t.carry);
+    (void)ek_dev_free(t.stats);
     t = cd_traj();
 }
 
@@ -363,14 +363,14 @@ extern "C" int ek_cards_close(ek_cards *h)
     for (cd_traj &t : h->trajs)
         cd_free_traj(t);
     for (uint32_t *p : h->jc)
-        (void)hipFree(p);
-    (void)hipFree(h->lo);
-    (void)hipFree(h->hi);
+        (void)ek_dev_free(p);
+    (void)ek_dev_free(h->lo);
+    (void)ek_dev_free(h->hi);
     for (hipEvent_t e : h->ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (h->s)
-        (void)hipStreamDestroy(h->s);
+        (void)ek_stream_destroy(h->s);
     delete h;
     return EK_OK;
 }
@@ -408,13 +408,13 @@ extern "C" int ek_cards_open(int device, int32_t f, int32_t n_states, ek_cards *
         if (rc != EK_OK)
             goto done;
     }
-    CD_HIP(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+    CD_HIP(ek_stream_create_flags(&h->s, hipStreamNonBlocking));
     for (hipEvent_t &e : h->ev)
-        CD_HIP(hipEventCreate(&e));
+        CD_HIP(ek_event_create(&e));
     for (int k = 0; k < 4; ++k)
-        CD_HIP(hipMalloc((void **)&h->jc[k], cd_cells(h, k) * sizeof(uint32_t)));
-    CD_HIP(hipMalloc((void **)&h->lo, (size_t)f * sizeof(int64_t)));
-    CD_HIP(hipMalloc((void **)&h->hi, (size_t)f * sizeof(int64_t)));
+        CD_HIP(ek_dev_malloc((void **)&h->jc[k], cd_cells(h, k) * sizeof(uint32_t)));
+    CD_HIP(ek_dev_malloc((void **)&h->lo, (size_t)f * sizeof(int64_t)));
+    CD_HIP(ek_dev_malloc((void **)&h->hi, (size_t)f * sizeof(int64_t)));
     *out = h;
     return EK_OK;
 done:
@@ -450,12 +450,12 @@ extern "C" int ek_cards_add(ek_cards *h, const uint8_t *X, int64_t frames)
     rc = ek_mi_check_memory(raw_b + 2 * code_b + part_b + carry_b + stats_b, "ek_cards_add");
     if (rc != EK_OK)
         return rc;
-    CD_HIP(hipMalloc((void **)&d_raw, raw_b));
-    CD_HIP(hipMalloc((void **)&t.S, code_b));
-    CD_HIP(hipMalloc((void **)&t.D, code_b));
-    CD_HIP(hipMalloc((void **)&t.part, part_b));
-    CD_HIP(hipMalloc((void **)&t.carry, carry_b));
-    CD_HIP(hipMalloc((void **)&t.stats, stats_b));
+    CD_HIP(ek_dev_malloc((void **)&d_raw, raw_b));
+    CD_HIP(ek_dev_malloc((void **)&t.S, code_b));
+    CD_HIP(ek_dev_malloc((void **)&t.D, code_b));
+    CD_HIP(ek_dev_malloc((void **)&t.part, part_b));
+    CD_HIP(ek_dev_malloc((void **)&t.carry, carry_b));
+    CD_HIP(ek_dev_malloc((void **)&t.stats, stats_b));
     CD_HIP(hipEventRecord(h->ev[0], h->s));
     CD_HIP(hipMemcpyAsync(d_raw, X, raw_b, hipMemcpyHostToDevice, h->s));
     ek_mi_launch_pack(d_raw, frames, h->f, t.tpad, t.S, h->s);
@@ -471,14 +471,14 @@ extern "C" int ek_cards_add(ek_cards *h, const uint8_t *X, int64_t frames)
     h->ms[0] = ms;
     CD_HIP(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
     h->ms[1] = ms;
-    (void)hipFree(d_raw);
+    (void)ek_dev_free(d_raw);
     h->trajs.push_back(t);
     h->n_obs += (uint64_t)frames;
     h->disordered = h->counted = false;
     return EK_OK;
 done:
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(d_raw);
+    (void)ek_dev_free(d_raw);
     cd_free_traj(t);
     return rc;
 }
@@ -546,7 +546,7 @@ extern "C" int ek_cards_disorder_codes(ek_cards *h, int32_t traj, uint8_t *out)
     rc = ek_mi_check_memory(raw_b, "ek_cards_disorder_codes");
     if (rc != EK_OK)
         return rc;
-    CD_HIP(hipMalloc((void **)&d_raw, raw_b));
+    CD_HIP(ek_dev_malloc((void **)&d_raw, raw_b));
     hipLaunchKernelGGL(cd_unpack_kernel, dim3((unsigned)(t.tpad / 64), (h->f + 63) / 64),
                        dim3(CD_WG), 0, h->s, t.D, t.frames, h->f, t.tpad, d_raw);
     CD_HIP(hipGetLastError());
@@ -554,7 +554,7 @@ extern "C" int ek_cards_disorder_codes(ek_cards *h, int32_t traj, uint8_t *out)
     CD_HIP(hipStreamSynchronize(h->s));
 done:
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(d_raw);
+    (void)ek_dev_free(d_raw);
     return rc;
 }
 
@@ -578,8 +578,8 @@ extern "C" int ek_cards_matrices(ek_cards *h, double *mi_out)
                             "ek_cards_matrices");
     if (rc != EK_OK)
         return rc;
-    CD_HIP(hipMalloc((void **)&d_col, (size_t)pairs * nmax * sizeof(uint32_t)));
-    CD_HIP(hipMalloc((void **)&d_mi, (size_t)pairs * 4 * sizeof(double)));
+    CD_HIP(ek_dev_malloc((void **)&d_col, (size_t)pairs * nmax * sizeof(uint32_t)));
+    CD_HIP(ek_dev_malloc((void **)&d_mi, (size_t)pairs * 4 * sizeof(double)));
     for (int k = 0; k < 3; ++k)
         CD_HIP(hipMemsetAsync(h->jc[k], 0, cd_cells(h, k) * sizeof(uint32_t), h->s));
     CD_HIP(hipEventRecord(h->ev[0], h->s));
@@ -610,8 +610,8 @@ extern "C" int ek_cards_matrices(ek_cards *h, double *mi_out)
     h->counted = true;
 done:
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(d_col);
-    (void)hipFree(d_mi);
+    (void)ek_dev_free(d_col);
+    (void)ek_dev_free(d_mi);
     return rc;
 }
 

@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "../../include/enspara_hip.h"
+#include "ek_track.h"
 
 #define EK_BLOCK 256          // threads per workgroup of the streaming kernels
 #define EK_WAVE 64

@@ -241,14 +241,14 @@ static int ent_kl_run(int device, int64_t rows, int64_t cols, const double *P, c
     hipStream_t s = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     float ms = 0.f;
-    ENT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    ENT_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
     for (hipEvent_t &e : ev)
-        ENT_HIP(hipEventCreate(&e));
-    ENT_HIP(hipMalloc((void **)&d_P, in_b));
-    ENT_HIP(hipMalloc((void **)&d_Q, in_b));
-    ENT_HIP(hipMalloc((void **)&d_a, out_b_));
-    ENT_HIP(hipMalloc((void **)&d_b, out_b_));
-    ENT_HIP(hipMalloc((void **)&d_flags, sizeof(uint32_t)));
+        ENT_HIP(ek_event_create(&e));
+    ENT_HIP(ek_dev_malloc((void **)&d_P, in_b));
+    ENT_HIP(ek_dev_malloc((void **)&d_Q, in_b));
+    ENT_HIP(ek_dev_malloc((void **)&d_a, out_b_));
+    ENT_HIP(ek_dev_malloc((void **)&d_b, out_b_));
+    ENT_HIP(ek_dev_malloc((void **)&d_flags, sizeof(uint32_t)));
     ENT_HIP(hipEventRecord(ev[0], s));
     ENT_HIP(hipMemcpyAsync(d_P, P, in_b, hipMemcpyHostToDevice, s));
     ENT_HIP(hipMemcpyAsync(d_Q, Q, in_b, hipMemcpyHostToDevice, s));
@@ -270,16 +270,16 @@ static int ent_kl_run(int device, int64_t rows, int64_t cols, const double *P, c
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_P);
-    (void)hipFree(d_Q);
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
-    (void)hipFree(d_flags);
+    (void)ek_dev_free(d_P);
+    (void)ek_dev_free(d_Q);
+    (void)ek_dev_free(d_a);
+    (void)ek_dev_free(d_b);
+    (void)ek_dev_free(d_flags);
     for (hipEvent_t e : ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }
 
@@ -314,11 +314,11 @@ extern "C" int ek_ent_shannon_rows(int device, int64_t rows, int64_t cols, const
     const int G = ent_group(cols);
     const dim3 grid(ent_row_blocks(rows, G)), wg(ENT_WG);
     const int norm = normalize ? 1 : 0;
-    ENT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    ENT_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
     for (hipEvent_t &e : ev)
-        ENT_HIP(hipEventCreate(&e));
-    ENT_HIP(hipMalloc((void **)&d_p, in_b));
-    ENT_HIP(hipMalloc((void **)&d_out, out_b));
+        ENT_HIP(ek_event_create(&e));
+    ENT_HIP(ek_dev_malloc((void **)&d_p, in_b));
+    ENT_HIP(ek_dev_malloc((void **)&d_out, out_b));
     ENT_HIP(hipEventRecord(ev[0], s));
     ENT_HIP(hipMemcpyAsync(d_p, p, in_b, hipMemcpyHostToDevice, s));
     ENT_HIP(hipEventRecord(ev[1], s));
@@ -340,13 +340,13 @@ extern "C" int ek_ent_shannon_rows(int device, int64_t rows, int64_t cols, const
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_p);
-    (void)hipFree(d_out);
+    (void)ek_dev_free(d_p);
+    (void)ek_dev_free(d_out);
     for (hipEvent_t e : ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }
 
@@ -424,16 +424,16 @@ extern "C" int ek_ent_kl_counts(int device, int32_t n, const double *P, int64_t 
     hipStream_t s = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float ms = 0.f;
-    ENT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    ENT_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
     for (hipEvent_t &e : ev)
-        ENT_HIP(hipEventCreate(&e));
-    ENT_HIP(hipMalloc((void **)&d_P, in_b));
-    ENT_HIP(hipMalloc((void **)&d_Q, in_b));
-    ENT_HIP(hipMalloc((void **)&d_out, out_b));
-    ENT_HIP(hipMalloc((void **)&d_ci, nz * sizeof(int32_t)));
-    ENT_HIP(hipMalloc((void **)&d_cj, nz * sizeof(int32_t)));
-    ENT_HIP(hipMalloc((void **)&d_cv, nz * sizeof(int64_t)));
-    ENT_HIP(hipMalloc((void **)&d_flags, sizeof(uint32_t)));
+        ENT_HIP(ek_event_create(&e));
+    ENT_HIP(ek_dev_malloc((void **)&d_P, in_b));
+    ENT_HIP(ek_dev_malloc((void **)&d_Q, in_b));
+    ENT_HIP(ek_dev_malloc((void **)&d_out, out_b));
+    ENT_HIP(ek_dev_malloc((void **)&d_ci, nz * sizeof(int32_t)));
+    ENT_HIP(ek_dev_malloc((void **)&d_cj, nz * sizeof(int32_t)));
+    ENT_HIP(ek_dev_malloc((void **)&d_cv, nz * sizeof(int64_t)));
+    ENT_HIP(ek_dev_malloc((void **)&d_flags, sizeof(uint32_t)));
     ENT_HIP(hipEventRecord(ev[0], s));
     ENT_HIP(hipMemcpyAsync(d_P, P, in_b, hipMemcpyHostToDevice, s));
     if (nnz > 0) {
@@ -464,18 +464,18 @@ extern "C" int ek_ent_kl_counts(int device, int32_t n, const double *P, int64_t 
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_P);
-    (void)hipFree(d_Q);
-    (void)hipFree(d_out);
-    (void)hipFree(d_ci);
-    (void)hipFree(d_cj);
-    (void)hipFree(d_cv);
-    (void)hipFree(d_flags);
+    (void)ek_dev_free(d_P);
+    (void)ek_dev_free(d_Q);
+    (void)ek_dev_free(d_out);
+    (void)ek_dev_free(d_ci);
+    (void)ek_dev_free(d_cj);
+    (void)ek_dev_free(d_cv);
+    (void)ek_dev_free(d_flags);
     for (hipEvent_t e : ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }
 
@@ -588,16 +588,16 @@ extern "C" int ek_ent_state_counts_open(int device, int32_t F, int32_t n_states,
     h->device = device;
     h->F = F;
     h->n_states = n_states;
-    ENT_HIP(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
-    ENT_HIP(hipMalloc((void **)&h->d_counts, bytes));
+    ENT_HIP(ek_stream_create_flags(&h->s, hipStreamNonBlocking));
+    ENT_HIP(ek_dev_malloc((void **)&h->d_counts, bytes));
     ENT_HIP(hipMemsetAsync(h->d_counts, 0, bytes, h->s));
     ENT_HIP(hipStreamSynchronize(h->s));
     *out = h;
     return EK_OK;
 done:
-    (void)hipFree(h->d_counts);
+    (void)ek_dev_free(h->d_counts);
     if (h->s)
-        (void)hipStreamDestroy(h->s);
+        (void)ek_stream_destroy(h->s);
     delete h;
     return rc;
 }
@@ -624,8 +624,8 @@ extern "C" int ek_ent_state_counts_add(ek_ent_state_counts *h, const uint8_t *co
                     (unsigned)(chunks < ENT_SC_MAX_GRID_Y ? chunks : ENT_SC_MAX_GRID_Y)),
         wg(ENT_WG);
     for (hipEvent_t &e : ev)
-        ENT_HIP(hipEventCreate(&e));
-    ENT_HIP(hipMalloc((void **)&d_codes, raw_b));
+        ENT_HIP(ek_event_create(&e));
+    ENT_HIP(ek_dev_malloc((void **)&d_codes, raw_b));
     ENT_HIP(hipEventRecord(ev[0], h->s));
     ENT_HIP(hipMemcpyAsync(d_codes, codes, raw_b, hipMemcpyHostToDevice, h->s));
     ENT_HIP(hipEventRecord(ev[1], h->s));
@@ -660,10 +660,10 @@ extern "C" int ek_ent_state_counts_add(ek_ent_state_counts *h, const uint8_t *co
     }
 done:
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(d_codes);
+    (void)ek_dev_free(d_codes);
     for (hipEvent_t e : ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     return rc;
 }
 
@@ -697,8 +697,8 @@ extern "C" int ek_ent_state_counts_close(ek_ent_state_counts *h)
         return EK_OK;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(h->d_counts);
-    (void)hipStreamDestroy(h->s);
+    (void)ek_dev_free(h->d_counts);
+    (void)ek_stream_destroy(h->s);
     delete h;
     return EK_OK;
 }

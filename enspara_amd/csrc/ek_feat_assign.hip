@@ -129,10 +129,10 @@ extern "C" int ek_feat_assign_nearest(ek_feat *k, int32_t metric, const void *ce
     const size_t cb = (size_t)K * (size_t)k->F * k->esize;
     if (cb > k->acent_cap) {
         FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(k->acent);
+        (void)ek_dev_free(k->acent);
         k->acent = nullptr;
         k->acent_cap = 0;
-        FE_HIP(hipMalloc(&k->acent, cb));
+        FE_HIP(ek_dev_malloc(&k->acent, cb));
         k->acent_cap = cb;
     }
     if (cb)
@@ -147,14 +147,14 @@ extern "C" int ek_feat_assign_nearest(ek_feat *k, int32_t metric, const void *ce
     parts = std::max((K + kper - 1) / kper, 1);
     if (parts > 1 && (size_t)parts * (size_t)k->n > k->apart_cap) {
         FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(k->apart_d);
-        (void)hipFree(k->apart_c);
+        (void)ek_dev_free(k->apart_d);
+        (void)ek_dev_free(k->apart_c);
         k->apart_d = nullptr;
         k->apart_c = nullptr;
         k->apart_cap = 0;
         const size_t cap = (size_t)parts * (size_t)k->n;
-        FE_HIP(hipMalloc((void **)&k->apart_d, cap * sizeof(double)));
-        FE_HIP(hipMalloc((void **)&k->apart_c, cap * sizeof(int32_t)));
+        FE_HIP(ek_dev_malloc((void **)&k->apart_d, cap * sizeof(double)));
+        FE_HIP(ek_dev_malloc((void **)&k->apart_c, cap * sizeof(int32_t)));
         k->apart_cap = cap;
     }
     feat_dispatch(k, metric, [&](auto t, auto m) {

@@ -140,14 +140,18 @@ static void feat_enqueue_steps(ek_feat *k, int nb, int32_t label0, int32_t count
 
 int feat_state_alloc(ek_feat *k)
 {
-    if (k->kdist)
-        return EK_OK;
+    // (each on its own: a call that failed part-way leaves the ones it got with the
+    // handle, and the next call must not take the first for all four)
     const size_t n1 = (size_t)std::max<int64_t>(k->n, 1);
     const size_t nb = (n1 + EK_BLOCK - 1) / EK_BLOCK;
-    FE_HIP(hipMalloc((void **)&k->kdist, n1 * sizeof(double)));
-    FE_HIP(hipMalloc((void **)&k->kassign, n1 * sizeof(int32_t)));
-    FE_HIP(hipMalloc((void **)&k->bm, nb * sizeof(FeatBlockMax)));
-    FE_HIP(hipMalloc((void **)&k->ctl, sizeof(FeatCtl)));
+    if (!k->kdist)
+        FE_HIP(ek_dev_malloc((void **)&k->kdist, n1 * sizeof(double)));
+    if (!k->kassign)
+        FE_HIP(ek_dev_malloc((void **)&k->kassign, n1 * sizeof(int32_t)));
+    if (!k->bm)
+        FE_HIP(ek_dev_malloc((void **)&k->bm, nb * sizeof(FeatBlockMax)));
+    if (!k->ctl)
+        FE_HIP(ek_dev_malloc((void **)&k->ctl, sizeof(FeatCtl)));
     return EK_OK;
 }
 
@@ -178,10 +182,10 @@ extern "C" int ek_feat_kcenters(ek_feat *k, int32_t metric, int32_t first_label,
         return rc;
     if (first_label + max_new + 1 > k->hist_cap) {
         FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(k->hist);
+        (void)ek_dev_free(k->hist);
         k->hist = nullptr;
         k->hist_cap = 0;
-        FE_HIP(hipMalloc((void **)&k->hist,
+        FE_HIP(ek_dev_malloc((void **)&k->hist,
                          (size_t)(first_label + max_new + 1) * sizeof(int64_t)));
         k->hist_cap = first_label + max_new + 1;
     }
@@ -386,7 +390,7 @@ int feat_shard_alloc(ek_feat *k, int32_t label)
     if (int rc = feat_state_alloc(k))
         return rc;
     if (!k->sctl) {
-        FE_HIP(hipMalloc((void **)&k->sctl, sizeof(FeatShardCtl)));
+        FE_HIP(ek_dev_malloc((void **)&k->sctl, sizeof(FeatShardCtl)));
         FE_HIP(hipMemsetAsync(k->sctl, 0, sizeof(FeatShardCtl), k->s));
     }
     if (label >= k->shist_cap) {
@@ -395,19 +399,31 @@ int feat_shard_alloc(ek_feat *k, int32_t label)
             cap *= 2;
         int64_t *hi = nullptr;
         double *hd = nullptr;
-        FE_HIP(hipMalloc((void **)&hi, (size_t)cap * sizeof(int64_t)));
-        FE_HIP(hipMalloc((void **)&hd, (size_t)cap * sizeof(double)));
-        FE_HIP(hipMemsetAsync(hi, 0xff, (size_t)cap * sizeof(int64_t), k->s));
-        FE_HIP(hipMemsetAsync(hd, 0, (size_t)cap * sizeof(double), k->s));
-        if (k->shist_cap) {
-            FE_HIP(hipMemcpyAsync(hi, k->shist_idx, (size_t)k->shist_cap * sizeof(int64_t),
-                                  hipMemcpyDeviceToDevice, k->s));
-            FE_HIP(hipMemcpyAsync(hd, k->shist_d, (size_t)k->shist_cap * sizeof(double),
-                                  hipMemcpyDeviceToDevice, k->s));
+        // (hi and hd belong to nobody until the handle takes them: every failure
+        // from here on gives both back)
+        hipError_t e = ek_dev_malloc((void **)&hi, (size_t)cap * sizeof(int64_t));
+        if (e == hipSuccess)
+            e = ek_dev_malloc((void **)&hd, (size_t)cap * sizeof(double));
+        if (e == hipSuccess)
+            e = hipMemsetAsync(hi, 0xff, (size_t)cap * sizeof(int64_t), k->s);
+        if (e == hipSuccess)
+            e = hipMemsetAsync(hd, 0, (size_t)cap * sizeof(double), k->s);
+        if (e == hipSuccess && k->shist_cap)
+            e = hipMemcpyAsync(hi, k->shist_idx, (size_t)k->shist_cap * sizeof(int64_t),
+                               hipMemcpyDeviceToDevice, k->s);
+        if (e == hipSuccess && k->shist_cap)
+            e = hipMemcpyAsync(hd, k->shist_d, (size_t)k->shist_cap * sizeof(double),
+                               hipMemcpyDeviceToDevice, k->s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(k->s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(k->s);
+            (void)ek_dev_free(hi);
+            (void)ek_dev_free(hd);
+            FE_HIP(e);
         }
-        FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(k->shist_idx);
-        (void)hipFree(k->shist_d);
+        (void)ek_dev_free(k->shist_idx);
+        (void)ek_dev_free(k->shist_d);
         k->shist_idx = hi;
         k->shist_d = hd;
         k->shist_cap = cap;

@@ -66,40 +66,40 @@ extern "C" void ek_feat_pam_release(ek_feat *k)
     if (!k || !k->pam)
         return;
     FeatPam &p = *k->pam;
-    (void)hipFree(p.MT);
-    (void)hipFree(p.col);
-    (void)hipFree(p.med);
-    (void)hipFree(p.idx);
-    (void)hipFree(p.ndist);
-    (void)hipFree(p.nassign);
-    (void)hipFree(p.amb);
-    (void)hipFree(p.best_d);
-    (void)hipFree(p.best_c);
-    (void)hipFree(p.counters);
-    (void)hipFree(p.blockcnt);
-    (void)hipFree(p.scan);
-    (void)hipFree(p.total);
-    (void)hipFree(p.part);
-    (void)hipFree(p.out2);
-    (void)hipFree(p.shapes);
-    (void)hipFree(p.ctl);
-    (void)hipFree(p.raw_dev);
-    (void)hipFree(p.jdev);
-    (void)hipFree(p.props_dev);
-    (void)hipFree(p.accept_dev);
-    (void)hipFree(p.win);
-    (void)hipFree(p.Y);
-    (void)hipFree(p.vecs);
-    (void)hipFree(p.blockcntW);
-    (void)hipFree(p.scanW);
-    (void)hipFree(p.totalW);
-    (void)hipFree(p.near_d);
-    (void)hipFree(p.near_c);
-    (void)hipFree(p.near_tick);
-    (void)hipFree(p.sh_blockcnt);
-    (void)hipFree(p.sh_scan);
-    (void)hipFree(p.sh_io);
-    (void)hipFree(p.sh_rows);
+    (void)ek_dev_free(p.MT);
+    (void)ek_dev_free(p.col);
+    (void)ek_dev_free(p.med);
+    (void)ek_dev_free(p.idx);
+    (void)ek_dev_free(p.ndist);
+    (void)ek_dev_free(p.nassign);
+    (void)ek_dev_free(p.amb);
+    (void)ek_dev_free(p.best_d);
+    (void)ek_dev_free(p.best_c);
+    (void)ek_dev_free(p.counters);
+    (void)ek_dev_free(p.blockcnt);
+    (void)ek_dev_free(p.scan);
+    (void)ek_dev_free(p.total);
+    (void)ek_dev_free(p.part);
+    (void)ek_dev_free(p.out2);
+    (void)ek_dev_free(p.shapes);
+    (void)ek_dev_free(p.ctl);
+    (void)ek_dev_free(p.raw_dev);
+    (void)ek_dev_free(p.jdev);
+    (void)ek_dev_free(p.props_dev);
+    (void)ek_dev_free(p.accept_dev);
+    (void)ek_dev_free(p.win);
+    (void)ek_dev_free(p.Y);
+    (void)ek_dev_free(p.vecs);
+    (void)ek_dev_free(p.blockcntW);
+    (void)ek_dev_free(p.scanW);
+    (void)ek_dev_free(p.totalW);
+    (void)ek_dev_free(p.near_d);
+    (void)ek_dev_free(p.near_c);
+    (void)ek_dev_free(p.near_tick);
+    (void)ek_dev_free(p.sh_blockcnt);
+    (void)ek_dev_free(p.sh_scan);
+    (void)ek_dev_free(p.sh_io);
+    (void)ek_dev_free(p.sh_rows);
     delete k->pam;
     k->pam = nullptr;
 }
@@ -819,16 +819,16 @@ int feat_pam_alloc(ek_feat *k, FeatPam &p, int32_t K)
     const size_t n = (size_t)std::max<int64_t>(k->n, 1);
     const size_t nb = (n + EK_BLOCK - 1) / EK_BLOCK;
     if (!p.ndist) {
-        FE_HIP(hipMalloc((void **)&p.ndist, n * sizeof(double)));
-        FE_HIP(hipMalloc((void **)&p.nassign, n * sizeof(int32_t)));
-        FE_HIP(hipMalloc((void **)&p.amb, n * sizeof(uint32_t)));
-        FE_HIP(hipMalloc((void **)&p.counters, 4 * sizeof(unsigned int)));
-        FE_HIP(hipMalloc((void **)&p.blockcnt, nb * sizeof(int32_t)));
-        FE_HIP(hipMalloc((void **)&p.scan, nb * sizeof(int64_t)));
-        FE_HIP(hipMalloc((void **)&p.total, sizeof(int64_t)));
-        FE_HIP(hipMalloc((void **)&p.idx, sizeof(int64_t)));
-        FE_HIP(hipMalloc((void **)&p.col, (size_t)k->F * k->esize));
-        FE_HIP(hipMalloc((void **)&p.out2, 2 * sizeof(double)));
+        FE_HIP(ek_dev_malloc((void **)&p.ndist, n * sizeof(double)));
+        FE_HIP(ek_dev_malloc((void **)&p.nassign, n * sizeof(int32_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.amb, n * sizeof(uint32_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.counters, 4 * sizeof(unsigned int)));
+        FE_HIP(ek_dev_malloc((void **)&p.blockcnt, nb * sizeof(int32_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.scan, nb * sizeof(int64_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.total, sizeof(int64_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.idx, sizeof(int64_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.col, (size_t)k->F * k->esize));
+        FE_HIP(ek_dev_malloc((void **)&p.out2, 2 * sizeof(double)));
         EkPwShape hs[2];
         const int64_t n_full = k->n / EK_PW_CHUNK;
         const int last_len = (int)(k->n - n_full * EK_PW_CHUNK);
@@ -840,21 +840,21 @@ int feat_pam_alloc(ek_feat *k, FeatPam &p, int32_t K)
         if (n_full > 0 && hs[0].n_leaves != EK_PW_FULL_LEAVES)
             return ek_set_error(EK_ESTATE, "ek_feat_pam_sweep: unexpected shape of a "
                                            "full chunk's pairwise sum");
-        FE_HIP(hipMalloc((void **)&p.shapes, sizeof(hs)));
+        FE_HIP(ek_dev_malloc((void **)&p.shapes, sizeof(hs)));
         FE_HIP(hipMemcpy(p.shapes, hs, sizeof(hs), hipMemcpyHostToDevice));
-        FE_HIP(hipMalloc((void **)&p.part, (2 * (size_t)std::max(p.n_leaves, 1) +
+        FE_HIP(ek_dev_malloc((void **)&p.part, (2 * (size_t)std::max(p.n_leaves, 1) +
                                             2 * (size_t)std::max(p.n_chunks, 1)) *
                                                sizeof(double)));
     }
     if (K > p.Kcap) {
         FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(p.MT);
-        (void)hipFree(p.med);
+        (void)ek_dev_free(p.MT);
+        (void)ek_dev_free(p.med);
         p.MT = nullptr;
         p.med = nullptr;
         p.Kcap = 0;
-        FE_HIP(hipMalloc((void **)&p.MT, (size_t)k->F * K * k->esize));
-        FE_HIP(hipMalloc((void **)&p.med, (size_t)K * sizeof(int64_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.MT, (size_t)k->F * K * k->esize));
+        FE_HIP(ek_dev_malloc((void **)&p.med, (size_t)K * sizeof(int64_t)));
         p.Kcap = K;
     }
     p.K = K;
@@ -862,18 +862,18 @@ int feat_pam_alloc(ek_feat *k, FeatPam &p, int32_t K)
     const int KC = (K + EK_BLOCK - 1) / EK_BLOCK;
     if (!p.near_tick) {
         const size_t nt = n / FN_MB + 2;
-        FE_HIP(hipMalloc((void **)&p.near_tick, nt * sizeof(unsigned int)));
+        FE_HIP(ek_dev_malloc((void **)&p.near_tick, nt * sizeof(unsigned int)));
         FE_HIP(hipMemsetAsync(p.near_tick, 0, nt * sizeof(unsigned int), k->s));
     }
     if (KC > 1 && KC > p.near_kc) {
         FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(p.near_d);
-        (void)hipFree(p.near_c);
+        (void)ek_dev_free(p.near_d);
+        (void)ek_dev_free(p.near_c);
         p.near_d = nullptr;
         p.near_c = nullptr;
         p.near_kc = 0;
-        FE_HIP(hipMalloc((void **)&p.near_d, n * (size_t)KC * sizeof(double)));
-        FE_HIP(hipMalloc((void **)&p.near_c, n * (size_t)KC * sizeof(int32_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.near_d, n * (size_t)KC * sizeof(double)));
+        FE_HIP(ek_dev_malloc((void **)&p.near_c, n * (size_t)KC * sizeof(int32_t)));
         p.near_kc = KC;
     }
     return EK_OK;
@@ -1042,27 +1042,27 @@ static int feat_pam_async_begin(ek_feat *k, FeatPam &p, int32_t K, const int64_t
                                 int64_t *raw_left_out, FeatPamCtl *hc_out)
 {
     if (!p.ctl) {
-        FE_HIP(hipMalloc((void **)&p.ctl, sizeof(FeatPamCtl)));
-        FE_HIP(hipMalloc((void **)&p.jdev, sizeof(int64_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.ctl, sizeof(FeatPamCtl)));
+        FE_HIP(ek_dev_malloc((void **)&p.jdev, sizeof(int64_t)));
         FE_HIP(hipMemsetAsync(p.jdev, 0, sizeof(int64_t), k->s));
     }
     if (!p.accept_dev || K > p.Kcap_async) {
         FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(p.accept_dev);
-        (void)hipFree(p.props_dev);
+        (void)ek_dev_free(p.accept_dev);
+        (void)ek_dev_free(p.props_dev);
         p.accept_dev = nullptr;
         p.props_dev = nullptr;
-        FE_HIP(hipMalloc((void **)&p.accept_dev, (size_t)K * sizeof(int32_t)));
-        FE_HIP(hipMalloc((void **)&p.props_dev, (size_t)K * sizeof(int64_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.accept_dev, (size_t)K * sizeof(int32_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.props_dev, (size_t)K * sizeof(int64_t)));
         p.Kcap_async = K;
     }
     const int64_t raw_left = *raw_left_out = proposals ? 0 : std::max<int64_t>(n_raw - *pos, 0);
     if (raw_left > p.raw_cap) {
         FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(p.raw_dev);
+        (void)ek_dev_free(p.raw_dev);
         p.raw_dev = nullptr;
         p.raw_cap = 0;
-        FE_HIP(hipMalloc((void **)&p.raw_dev, (size_t)raw_left * sizeof(uint32_t)));
+        FE_HIP(ek_dev_malloc((void **)&p.raw_dev, (size_t)raw_left * sizeof(uint32_t)));
         p.raw_cap = raw_left;
     }
     if (raw_left > 0)       // (positions on the device count from *pos)
@@ -1113,11 +1113,37 @@ static int feat_pam_async_end(ek_feat *k, FeatPam &p, int32_t K, const FeatPamCt
     return EK_OK;
 }
 
+static int feat_pam_sweep_run(ek_feat *k, int32_t metric, int32_t n_medoids,
+                              int64_t *medoids, const int64_t *proposals,
+                              const uint32_t *raw, int64_t n_raw, int64_t *pos,
+                              double *dist_io, int32_t *assign_io,
+                              int32_t *accept, int32_t *cid_io, int32_t *status);
+
+// The sweep's scratch is made in groups that are tested by their first buffer
+// (feat_pam_alloc, the windows, feat_pam_async_begin): a HIP call that fails part-way
+// would leave a group half made for the next sweep to take for whole.  A sweep that
+// fails so gives all of it back; the next one makes it again.
 extern "C" int ek_feat_pam_sweep(ek_feat *k, int32_t metric, int32_t n_medoids,
                                  int64_t *medoids, const int64_t *proposals,
                                  const uint32_t *raw, int64_t n_raw, int64_t *pos,
                                  double *dist_io, int32_t *assign_io,
                                  int32_t *accept, int32_t *cid_io, int32_t *status)
+{
+    const int rc = feat_pam_sweep_run(k, metric, n_medoids, medoids, proposals, raw, n_raw,
+                                      pos, dist_io, assign_io, accept, cid_io, status);
+    if (rc == EK_EHIP && k && k->pam) {
+        if (k->s)
+            (void)hipStreamSynchronize(k->s);
+        ek_feat_pam_release(k);
+    }
+    return rc;
+}
+
+static int feat_pam_sweep_run(ek_feat *k, int32_t metric, int32_t n_medoids,
+                              int64_t *medoids, const int64_t *proposals,
+                              const uint32_t *raw, int64_t n_raw, int64_t *pos,
+                              double *dist_io, int32_t *assign_io,
+                              int32_t *accept, int32_t *cid_io, int32_t *status)
 {
     if (!k || !medoids || !dist_io || !assign_io || !accept || !cid_io || !status ||
         !pos || n_medoids < 1 || metric < 0 || metric > 2)
@@ -1179,12 +1205,12 @@ extern "C" int ek_feat_pam_sweep(ek_feat *k, int32_t metric, int32_t n_medoids,
     const bool fw_big = (int64_t)k->n * k->F * k->esize >= (64ll << 20);
     if (!getenv("EK_FEAT_PAM_SYNC") && !(fw_env && fw_env[0] == '0')) {
         if (!p.win) {
-            FE_HIP(hipMalloc((void **)&p.win, sizeof(FeatWin)));
-            FE_HIP(hipMalloc((void **)&p.Y, (size_t)FEAT_WIN * k->F * k->esize));
-            FE_HIP(hipMalloc((void **)&p.vecs, (size_t)FEAT_WIN * k->n * sizeof(double)));
-            FE_HIP(hipMalloc((void **)&p.blockcntW, (size_t)FEAT_WIN * nb * sizeof(int32_t)));
-            FE_HIP(hipMalloc((void **)&p.scanW, (size_t)FEAT_WIN * nb * sizeof(int64_t)));
-            FE_HIP(hipMalloc((void **)&p.totalW, FEAT_WIN * sizeof(int64_t)));
+            FE_HIP(ek_dev_malloc((void **)&p.win, sizeof(FeatWin)));
+            FE_HIP(ek_dev_malloc((void **)&p.Y, (size_t)FEAT_WIN * k->F * k->esize));
+            FE_HIP(ek_dev_malloc((void **)&p.vecs, (size_t)FEAT_WIN * k->n * sizeof(double)));
+            FE_HIP(ek_dev_malloc((void **)&p.blockcntW, (size_t)FEAT_WIN * nb * sizeof(int32_t)));
+            FE_HIP(ek_dev_malloc((void **)&p.scanW, (size_t)FEAT_WIN * nb * sizeof(int64_t)));
+            FE_HIP(ek_dev_malloc((void **)&p.totalW, FEAT_WIN * sizeof(int64_t)));
         }
         int64_t raw_left = 0;
         FeatPamCtl hc;

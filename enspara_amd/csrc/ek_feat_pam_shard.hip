@@ -181,13 +181,17 @@ static int feat_shard_pam_alloc(ek_feat *k)
             return ek_set_error(EK_ENOMEM, "ek_feat_pam: out of host memory");
     }
     FeatPam &p = *k->pam;
-    if (!p.sh_io) {
-        const size_t nb = (size_t)std::max<int64_t>((k->n + EK_BLOCK - 1) / EK_BLOCK, 1);
-        FE_HIP(hipMalloc((void **)&p.sh_blockcnt, EK_PAM_WIN * nb * sizeof(int32_t)));
-        FE_HIP(hipMalloc((void **)&p.sh_scan, EK_PAM_WIN * nb * sizeof(int64_t)));
-        FE_HIP(hipMalloc((void **)&p.sh_io, 3 * EK_PAM_WIN * sizeof(int64_t)));
-        FE_HIP(hipMalloc((void **)&p.sh_rows, 2 * FS_GATHER * sizeof(int64_t)));
-    }
+    // (each on its own: a call that failed part-way must not leave the next one a
+    // group it takes for whole)
+    const size_t nb = (size_t)std::max<int64_t>((k->n + EK_BLOCK - 1) / EK_BLOCK, 1);
+    if (!p.sh_blockcnt)
+        FE_HIP(ek_dev_malloc((void **)&p.sh_blockcnt, EK_PAM_WIN * nb * sizeof(int32_t)));
+    if (!p.sh_scan)
+        FE_HIP(ek_dev_malloc((void **)&p.sh_scan, EK_PAM_WIN * nb * sizeof(int64_t)));
+    if (!p.sh_io)
+        FE_HIP(ek_dev_malloc((void **)&p.sh_io, 3 * EK_PAM_WIN * sizeof(int64_t)));
+    if (!p.sh_rows)
+        FE_HIP(ek_dev_malloc((void **)&p.sh_rows, 2 * FS_GATHER * sizeof(int64_t)));
     return EK_OK;
 }
 
@@ -305,8 +309,12 @@ extern "C" int ek_feat_pam_begin(ek_feat *k, int32_t metric, const void *table_d
     p.K = n_medoids;
     if (k->n == 0)
         return EK_OK;           // (nothing of this shard is ever looked at)
-    if ((rc = feat_pam_alloc(k, p, n_medoids)))
+    if ((rc = feat_pam_alloc(k, p, n_medoids))) {
+        // (a group of the scratch may be half made: all of it goes, ek_feat_pam_sweep)
+        (void)hipStreamSynchronize(k->s);
+        ek_feat_pam_release(k);
         return rc;
+    }
     feat_dispatch_size(k, [&](auto t) {
         using T = typename decltype(t)::type;
         hipLaunchKernelGGL(feat_shard_table_kernel<T>, dim3(n_medoids), dim3(EK_BLOCK), 0, k->s,

@@ -85,23 +85,23 @@ extern "C" int ek_feat_destroy(ek_feat *k)
     (void)hipSetDevice(k->device);
     if (k->s)
         (void)hipStreamSynchronize(k->s);
-    (void)hipFree(k->tiles);
-    (void)hipFree(k->stage);
-    (void)hipFree(k->y);
-    (void)hipFree(k->out);
-    (void)hipFree(k->kdist);
-    (void)hipFree(k->kassign);
-    (void)hipFree(k->bm);
-    (void)hipFree(k->ctl);
-    (void)hipFree(k->hist);
-    (void)hipFree(k->sctl);
-    (void)hipFree(k->shist_idx);
-    (void)hipFree(k->shist_d);
-    (void)hipFree(k->acent);
-    (void)hipFree(k->apart_d);
-    (void)hipFree(k->apart_c);
+    (void)ek_dev_free(k->tiles);
+    (void)ek_dev_free(k->stage);
+    (void)ek_dev_free(k->y);
+    (void)ek_dev_free(k->out);
+    (void)ek_dev_free(k->kdist);
+    (void)ek_dev_free(k->kassign);
+    (void)ek_dev_free(k->bm);
+    (void)ek_dev_free(k->ctl);
+    (void)ek_dev_free(k->hist);
+    (void)ek_dev_free(k->sctl);
+    (void)ek_dev_free(k->shist_idx);
+    (void)ek_dev_free(k->shist_d);
+    (void)ek_dev_free(k->acent);
+    (void)ek_dev_free(k->apart_d);
+    (void)ek_dev_free(k->apart_c);
     if (k->s && k->own_stream)
-        (void)hipStreamDestroy(k->s);
+        (void)ek_stream_destroy(k->s);
     delete k;
     return EK_OK;
 }
@@ -135,16 +135,16 @@ extern "C" int ek_feat_create_sharded(int device, int64_t n_samples,
         k->s = (hipStream_t)stream;
         k->own_stream = false;
     } else {
-        e = hipStreamCreateWithFlags(&k->s, hipStreamNonBlocking);
+        e = ek_stream_create_flags(&k->s, hipStreamNonBlocking);
     }
     if (e == hipSuccess)
-        e = hipMalloc(&k->tiles, tb);
+        e = ek_dev_malloc(&k->tiles, tb);
     if (e == hipSuccess)
         e = hipMemsetAsync(k->tiles, 0, tb, k->s);
     if (e == hipSuccess)
-        e = hipMalloc(&k->y, (size_t)n_features * k->esize);
+        e = ek_dev_malloc(&k->y, (size_t)n_features * k->esize);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&k->out,
+        e = ek_dev_malloc((void **)&k->out,
                       (size_t)std::max<int64_t>(n_samples, 1) * sizeof(double));
     if (e != hipSuccess) {
         ek_feat_destroy(k);
@@ -175,10 +175,10 @@ extern "C" int ek_feat_load(ek_feat *k, const void *X, int64_t first,
     chunk = std::min<int64_t>(chunk, (count + EK_TILE - 1) / EK_TILE * EK_TILE);
     if (chunk > k->stage_rows) {
         FE_HIP(hipStreamSynchronize(k->s));
-        (void)hipFree(k->stage);
+        (void)ek_dev_free(k->stage);
         k->stage = nullptr;
         k->stage_rows = 0;
-        FE_HIP(hipMalloc(&k->stage, (size_t)chunk * row));
+        FE_HIP(ek_dev_malloc(&k->stage, (size_t)chunk * row));
         k->stage_rows = chunk;
     }
     for (int64_t done = 0; done < count; done += chunk) {

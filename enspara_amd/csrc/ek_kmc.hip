@@ -443,7 +443,7 @@ struct KmcScope {
     {
         if (n >= 24)
             return hipErrorOutOfMemory;
-        hipError_t e = hipMalloc((void **)p, bytes ? bytes : 1);
+        hipError_t e = ek_dev_malloc((void **)p, bytes ? bytes : 1);
         if (e == hipSuccess)
             ptr[n++] = (void *)*p;
         return e;
@@ -451,7 +451,7 @@ struct KmcScope {
     hipError_t events()
     {
         for (hipEvent_t &e : ev) {
-            hipError_t r = hipEventCreate(&e);
+            hipError_t r = ek_event_create(&e);
             if (r != hipSuccess)
                 return r;
         }
@@ -464,12 +464,12 @@ struct KmcScope {
         if (own)
             (void)hipStreamSynchronize(own);
         for (int i = 0; i < n; ++i)
-            (void)hipFree(ptr[i]);
+            (void)ek_dev_free(ptr[i]);
         for (hipEvent_t e : ev)
             if (e)
-                (void)hipEventDestroy(e);
+                (void)ek_event_destroy(e);
         if (own)
-            (void)hipStreamDestroy(own);
+            (void)ek_stream_destroy(own);
     }
 };
 
@@ -536,13 +536,13 @@ extern "C" int ek_kmc_create(int device, int32_t n_states, const int64_t *indptr
     h->device = device;
     h->n = n_states;
     h->nnz = nnz;
-    hipError_t e = hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking);
+    hipError_t e = ek_stream_create_flags(&h->s, hipStreamNonBlocking);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&h->d_indptr, ib);
+        e = ek_dev_malloc((void **)&h->d_indptr, ib);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&h->d_cols, cb ? cb : 1);
+        e = ek_dev_malloc((void **)&h->d_cols, cb ? cb : 1);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&h->d_cdf, fb ? fb : 1);
+        e = ek_dev_malloc((void **)&h->d_cdf, fb ? fb : 1);
     if (e == hipSuccess)
         e = hipMemcpyAsync(h->d_indptr, indptr, ib, hipMemcpyHostToDevice, h->s);
     if (e == hipSuccess && nnz > 0)
@@ -553,11 +553,11 @@ extern "C" int ek_kmc_create(int device, int32_t n_states, const int64_t *indptr
         e = hipStreamSynchronize(h->s);
     if (e != hipSuccess) {
         rc = ek_set_error(EK_EHIP, "ek_kmc_create: %s", hipGetErrorString(e));
-        (void)hipFree(h->d_indptr);
-        (void)hipFree(h->d_cols);
-        (void)hipFree(h->d_cdf);
+        (void)ek_dev_free(h->d_indptr);
+        (void)ek_dev_free(h->d_cols);
+        (void)ek_dev_free(h->d_cdf);
         if (h->s)
-            (void)hipStreamDestroy(h->s);
+            (void)ek_stream_destroy(h->s);
         delete h;
         return rc;
     }
@@ -571,10 +571,10 @@ extern "C" int ek_kmc_destroy(ek_kmc *h)
         return EK_OK;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(h->d_indptr);
-    (void)hipFree(h->d_cols);
-    (void)hipFree(h->d_cdf);
-    (void)hipStreamDestroy(h->s);
+    (void)ek_dev_free(h->d_indptr);
+    (void)ek_dev_free(h->d_cols);
+    (void)ek_dev_free(h->d_cdf);
+    (void)ek_stream_destroy(h->s);
     delete h;
     return EK_OK;
 }
@@ -765,7 +765,7 @@ extern "C" int ek_kmc_ensemble(int device, int32_t n, const double *T, const int
            *d_obs = nullptr;
     int64_t *d_colptr = nullptr;
     int32_t *d_rows = nullptr;
-    KMC_HIP(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
+    KMC_HIP(ek_stream_create_flags(&sc.own, hipStreamNonBlocking));
     hipStream_t s = sc.own;
     KMC_HIP(sc.events());
     if (dense) {
@@ -887,7 +887,7 @@ extern "C" int ek_kmc_fret_probs(int device, uint64_t seed, int64_t chain, int64
     KmcDist D;
     int32_t *d_s = nullptr;
     double *d_E = nullptr;
-    KMC_HIP(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
+    KMC_HIP(ek_stream_create_flags(&sc.own, hipStreamNonBlocking));
     hipStream_t s = sc.own;
     KMC_HIP(sc.events());
     KMC_HIP(sc.alloc(&d_s, (size_t)n * sizeof(int32_t)));

@@ -160,21 +160,21 @@ extern "C" int ek_krylov_destroy(ek_krylov *k)
     (void)hipSetDevice(k->device);
     if (k->s)
         (void)hipStreamSynchronize(k->s);
-    (void)hipFree(k->indptr);
-    (void)hipFree(k->indices);
-    (void)hipFree(k->data);
-    (void)hipFree(k->V);
-    (void)hipFree(k->w);
-    (void)hipFree(k->w2);
-    (void)hipFree(k->part);
-    (void)hipFree(k->tmp);
-    (void)hipFree(k->h);
-    (void)hipFree(k->q);
-    (void)hipFree(k->hcols);
-    (void)hipFree(k->t[0]);
-    (void)hipFree(k->t[1]);
+    (void)ek_dev_free(k->indptr);
+    (void)ek_dev_free(k->indices);
+    (void)ek_dev_free(k->data);
+    (void)ek_dev_free(k->V);
+    (void)ek_dev_free(k->w);
+    (void)ek_dev_free(k->w2);
+    (void)ek_dev_free(k->part);
+    (void)ek_dev_free(k->tmp);
+    (void)ek_dev_free(k->h);
+    (void)ek_dev_free(k->q);
+    (void)ek_dev_free(k->hcols);
+    (void)ek_dev_free(k->t[0]);
+    (void)ek_dev_free(k->t[1]);
     if (k->s)
-        (void)hipStreamDestroy(k->s);
+        (void)ek_stream_destroy(k->s);
     delete k;
     return EK_OK;
 }
@@ -195,10 +195,10 @@ extern "C" int ek_krylov_create(int device, int64_t n, const int64_t *indptr,
     k->nnz = indptr[n];
     k->m_max = m_max;
     const size_t nz = (size_t)std::max<int64_t>(k->nnz, 1);
-    hipError_t e = hipStreamCreateWithFlags(&k->s, hipStreamNonBlocking);
+    hipError_t e = ek_stream_create_flags(&k->s, hipStreamNonBlocking);
 #define KA(ptr, bytes)                                                         \
     if (e == hipSuccess)                                                       \
-        e = hipMalloc((void **)&(ptr), (bytes));
+        e = ek_dev_malloc((void **)&(ptr), (bytes));
     KA(k->indptr, (size_t)(n + 1) * sizeof(int64_t));
     KA(k->indices, nz * sizeof(int32_t));
     KA(k->data, nz * sizeof(double));

@@ -67,7 +67,7 @@ void ek_lu_mark(int kind, hipStream_t s)
     if (!g_lu_timing || g_lu_n_marks >= LU_MAX_MARKS)
         return;
     hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess)
+    if (ek_event_create(&e) != hipSuccess)
         return;
     (void)hipEventRecord(e, s);
     g_lu_ev[g_lu_n_marks] = e;
@@ -86,7 +86,7 @@ void ek_lu_collect(void)
             g_lu_ms[g_lu_kind[i]] += (double)ms;
     }
     for (int i = 0; i < g_lu_n_marks; ++i)
-        (void)hipEventDestroy(g_lu_ev[i]);
+        (void)ek_event_destroy(g_lu_ev[i]);
     g_lu_n_marks = 0;
     for (int k = 0; k < 2; ++k) {
         g_lu_flops[k] = g_lu_flops_run[k];

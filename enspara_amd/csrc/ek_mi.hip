@@ -324,12 +324,12 @@ extern "C" int ek_mi_close(ek_mi *h)
     (void)hipSetDevice(h->device);
     if (h->s)
         (void)hipStreamSynchronize(h->s);
-    (void)hipFree(h->jc);
+    (void)ek_dev_free(h->jc);
     for (hipEvent_t e : h->ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (h->s)
-        (void)hipStreamDestroy(h->s);
+        (void)ek_stream_destroy(h->s);
     delete h;
     return EK_OK;
 }
@@ -362,10 +362,10 @@ extern "C" int ek_mi_open(int device, int32_t fx, int32_t fy, int32_t nx, int32_
     rc = ek_mi_check_memory(h->cells * sizeof(uint32_t), "ek_mi_open");
     if (rc != EK_OK)
         goto done;
-    MI_HIP(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+    MI_HIP(ek_stream_create_flags(&h->s, hipStreamNonBlocking));
     for (hipEvent_t &e : h->ev)
-        MI_HIP(hipEventCreate(&e));
-    MI_HIP(hipMalloc((void **)&h->jc, h->cells * sizeof(uint32_t)));
+        MI_HIP(ek_event_create(&e));
+    MI_HIP(ek_dev_malloc((void **)&h->jc, h->cells * sizeof(uint32_t)));
     MI_HIP(hipMemsetAsync(h->jc, 0, h->cells * sizeof(uint32_t), h->s));
     MI_HIP(hipStreamSynchronize(h->s));
     *out = h;
@@ -401,10 +401,10 @@ extern "C" int ek_mi_add(ek_mi *h, const uint8_t *X, const uint8_t *Y, int64_t f
     rc = ek_mi_check_memory(raw_b + cx_b + cy_b, "ek_mi_add");
     if (rc != EK_OK)
         return rc;
-    MI_HIP(hipMalloc((void **)&d_raw, raw_b));
-    MI_HIP(hipMalloc((void **)&d_cx, cx_b));
+    MI_HIP(ek_dev_malloc((void **)&d_raw, raw_b));
+    MI_HIP(ek_dev_malloc((void **)&d_cx, cx_b));
     if (Y)
-        MI_HIP(hipMalloc((void **)&d_cy, cy_b));
+        MI_HIP(ek_dev_malloc((void **)&d_cy, cy_b));
     MI_HIP(hipEventRecord(h->ev[0], h->s));
     MI_HIP(hipMemcpyAsync(d_raw, X, (size_t)frames * h->fx, hipMemcpyHostToDevice, h->s));
     ek_mi_launch_pack(d_raw, frames, h->fx, tpad, d_cx, h->s);
@@ -424,9 +424,9 @@ extern "C" int ek_mi_add(ek_mi *h, const uint8_t *X, const uint8_t *Y, int64_t f
     h->ms[1] = ms;
 done:
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(d_raw);
-    (void)hipFree(d_cx);
-    (void)hipFree(d_cy);
+    (void)ek_dev_free(d_raw);
+    (void)ek_dev_free(d_cx);
+    (void)ek_dev_free(d_cy);
     return rc;
 }
 
@@ -475,8 +475,8 @@ extern "C" int ek_mi_information(ek_mi *h, double *mi_out)
                          "ek_mi_information");
     if (rc != EK_OK)
         return rc;
-    MI_HIP(hipMalloc((void **)&d_col, (size_t)pairs * h->ny * sizeof(uint32_t)));
-    MI_HIP(hipMalloc((void **)&d_mi, (size_t)pairs * sizeof(double)));
+    MI_HIP(ek_dev_malloc((void **)&d_col, (size_t)pairs * h->ny * sizeof(uint32_t)));
+    MI_HIP(ek_dev_malloc((void **)&d_mi, (size_t)pairs * sizeof(double)));
     MI_HIP(hipEventRecord(h->ev[0], h->s));
     ek_mi_launch_info(h->jc, pairs, h->nx, h->ny, d_col, d_mi, h->s);
     MI_HIP(hipEventRecord(h->ev[3], h->s));
@@ -488,8 +488,8 @@ extern "C" int ek_mi_information(ek_mi *h, double *mi_out)
     h->ms[2] = ms;
 done:
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(d_col);
-    (void)hipFree(d_mi);
+    (void)ek_dev_free(d_col);
+    (void)ek_dev_free(d_mi);
     return rc;
 }
 

@@ -433,16 +433,16 @@ static void msm_scratch_release(EkMsmScratch *w)
 {
     if (!w)
         return;
-    (void)hipFree(w->c);
-    (void)hipFree(w->cnt);
-    (void)hipFree(w->off);
-    (void)hipFree(w->start);
-    (void)hipFree(w->cstart);
-    (void)hipFree(w->table);
-    (void)hipFree(w->bad);
-    (void)hipFree(w->rows);
-    (void)hipFree(w->cols);
-    (void)hipFree(w->vals);
+    (void)ek_dev_free(w->c);
+    (void)ek_dev_free(w->cnt);
+    (void)ek_dev_free(w->off);
+    (void)ek_dev_free(w->start);
+    (void)ek_dev_free(w->cstart);
+    (void)ek_dev_free(w->table);
+    (void)ek_dev_free(w->bad);
+    (void)ek_dev_free(w->rows);
+    (void)ek_dev_free(w->cols);
+    (void)ek_dev_free(w->vals);
     *w = EkMsmScratch();
 }
 
@@ -459,10 +459,10 @@ static hipError_t msm_grow(P *&ptr, int64_t &cap, int64_t need)
 {
     if (need <= cap)
         return hipSuccess;
-    (void)hipFree(ptr);
+    (void)ek_dev_free(ptr);
     ptr = nullptr;
     cap = 0;
-    const hipError_t e = hipMalloc((void **)&ptr, (size_t)need * sizeof(*ptr));
+    const hipError_t e = ek_dev_malloc((void **)&ptr, (size_t)need * sizeof(*ptr));
     if (e == hipSuccess)
         cap = need;
     return e;
@@ -639,8 +639,8 @@ extern "C" int ek_msm_counts(int device, const int32_t *assigns,
         goto done;
     }
     MSM_HIP(hipSetDevice(device));
-    MSM_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    MSM_HIP(hipMalloc((void **)&d_a, (size_t)n * sizeof(int32_t)));
+    MSM_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
+    MSM_HIP(ek_dev_malloc((void **)&d_a, (size_t)n * sizeof(int32_t)));
     MSM_HIP(hipMemcpyAsync(d_a, assigns, (size_t)n * sizeof(int32_t),
                            hipMemcpyHostToDevice, s));
     rc = msm_counts_device(s, w, d_a, starts, n, n_trj, lag_time, sliding_window,
@@ -649,11 +649,11 @@ extern "C" int ek_msm_counts(int device, const int32_t *assigns,
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_a);
+    (void)ek_dev_free(d_a);
     msm_scratch_release(&w);
     free(starts);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }
 
@@ -751,11 +751,11 @@ extern "C" int ek_msm_row_normalize(int device, const int64_t *indptr,
             return ek_set_error(EK_EHIP, "hipSetDevice(%d): %s", device,
                                 hipGetErrorString(e0));
     }
-    MSM_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    MSM_HIP(hipMalloc((void **)&d_ip, (size_t)(n_rows + 1) * sizeof(int64_t)));
-    MSM_HIP(hipMalloc((void **)&d_in, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
-    MSM_HIP(hipMalloc((void **)&d_out, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
-    MSM_HIP(hipMalloc((void **)&d_rs, (size_t)n_rows * sizeof(double)));
+    MSM_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
+    MSM_HIP(ek_dev_malloc((void **)&d_ip, (size_t)(n_rows + 1) * sizeof(int64_t)));
+    MSM_HIP(ek_dev_malloc((void **)&d_in, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
+    MSM_HIP(ek_dev_malloc((void **)&d_out, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
+    MSM_HIP(ek_dev_malloc((void **)&d_rs, (size_t)n_rows * sizeof(double)));
     MSM_HIP(hipMemcpyAsync(d_ip, indptr, (size_t)(n_rows + 1) * sizeof(int64_t),
                            hipMemcpyHostToDevice, s));
     if (nnz > 0)
@@ -774,11 +774,11 @@ extern "C" int ek_msm_row_normalize(int device, const int64_t *indptr,
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_ip);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_rs);
+    (void)ek_dev_free(d_ip);
+    (void)ek_dev_free(d_in);
+    (void)ek_dev_free(d_out);
+    (void)ek_dev_free(d_rs);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }

@@ -363,10 +363,10 @@ extern "C" int ek_msm_bace_prune(int device, int32_t n, const double *c, const d
             return ek_set_error(EK_EHIP, "hipSetDevice(%d): %s", device,
                                 hipGetErrorString(e0));
     }
-    BACE_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    BACE_HIP(hipMalloc((void **)&d_c, nn * sizeof(double)));
-    BACE_HIP(hipMalloc((void **)&d_w, (size_t)n * sizeof(double)));
-    BACE_HIP(hipMalloc((void **)&d_d, (size_t)n * sizeof(float)));
+    BACE_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
+    BACE_HIP(ek_dev_malloc((void **)&d_c, nn * sizeof(double)));
+    BACE_HIP(ek_dev_malloc((void **)&d_w, (size_t)n * sizeof(double)));
+    BACE_HIP(ek_dev_malloc((void **)&d_d, (size_t)n * sizeof(float)));
     BACE_HIP(hipMemcpyAsync(d_c, c, nn * sizeof(double), hipMemcpyHostToDevice, s));
     BACE_HIP(hipMemcpyAsync(d_w, w, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
     {
@@ -381,11 +381,11 @@ extern "C" int ek_msm_bace_prune(int device, int32_t n, const double *c, const d
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_c);
-    (void)hipFree(d_w);
-    (void)hipFree(d_d);
+    (void)ek_dev_free(d_c);
+    (void)ek_dev_free(d_w);
+    (void)ek_dev_free(d_d);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }
 
@@ -461,16 +461,16 @@ extern "C" int ek_msm_bace_run(int device, int32_t n, const double *c, const dou
                                 hipGetErrorString(e0));
         }
     }
-    BACE_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    BACE_HIP(hipMalloc((void **)&d_c, nn * sizeof(double)));
-    BACE_HIP(hipMalloc((void **)&d_dmat, nn * sizeof(float)));
-    BACE_HIP(hipMalloc((void **)&d_w, (size_t)n * sizeof(double)));
-    BACE_HIP(hipMalloc((void **)&d_um, (size_t)n * sizeof(int32_t)));
-    BACE_HIP(hipMalloc((void **)&d_kept, (size_t)n * sizeof(int32_t)));
-    BACE_HIP(hipMalloc((void **)&d_list, (n_list ? n_list : 1) * sizeof(int2)));
-    BACE_HIP(hipMalloc((void **)&d_part, (size_t)nb_max * sizeof(BaceMax)));
-    BACE_HIP(hipMalloc((void **)&d_rec, (size_t)n_rec * sizeof(BaceRec)));
-    BACE_HIP(hipMalloc((void **)&d_cur, sizeof(BaceCur)));
+    BACE_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
+    BACE_HIP(ek_dev_malloc((void **)&d_c, nn * sizeof(double)));
+    BACE_HIP(ek_dev_malloc((void **)&d_dmat, nn * sizeof(float)));
+    BACE_HIP(ek_dev_malloc((void **)&d_w, (size_t)n * sizeof(double)));
+    BACE_HIP(ek_dev_malloc((void **)&d_um, (size_t)n * sizeof(int32_t)));
+    BACE_HIP(ek_dev_malloc((void **)&d_kept, (size_t)n * sizeof(int32_t)));
+    BACE_HIP(ek_dev_malloc((void **)&d_list, (n_list ? n_list : 1) * sizeof(int2)));
+    BACE_HIP(ek_dev_malloc((void **)&d_part, (size_t)nb_max * sizeof(BaceMax)));
+    BACE_HIP(ek_dev_malloc((void **)&d_rec, (size_t)n_rec * sizeof(BaceRec)));
+    BACE_HIP(ek_dev_malloc((void **)&d_cur, sizeof(BaceCur)));
     BACE_HIP(hipMemcpyAsync(d_c, c, nn * sizeof(double), hipMemcpyHostToDevice, s));
     BACE_HIP(hipMemcpyAsync(d_w, w, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
     // (bace.py:88-89: unmerged starts as the kept mask)
@@ -513,17 +513,17 @@ extern "C" int ek_msm_bace_run(int device, int32_t n, const double *c, const dou
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_c);
-    (void)hipFree(d_dmat);
-    (void)hipFree(d_w);
-    (void)hipFree(d_um);
-    (void)hipFree(d_kept);
-    (void)hipFree(d_list);
-    (void)hipFree(d_part);
-    (void)hipFree(d_rec);
-    (void)hipFree(d_cur);
+    (void)ek_dev_free(d_c);
+    (void)ek_dev_free(d_dmat);
+    (void)ek_dev_free(d_w);
+    (void)ek_dev_free(d_um);
+    (void)ek_dev_free(d_kept);
+    (void)ek_dev_free(d_list);
+    (void)ek_dev_free(d_part);
+    (void)ek_dev_free(d_rec);
+    (void)ek_dev_free(d_cur);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     delete[] h_mask;
     delete[] h_list;
     return rc;

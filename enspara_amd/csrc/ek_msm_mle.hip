@@ -230,7 +230,7 @@ msm_mle_prinz_kernel(int32_t n, int32_t n_levels,
 template <typename T>
 static hipError_t mle_upload(T **dst, const T *src, int64_t count, hipStream_t s)
 {
-    hipError_t e = hipMalloc((void **)dst, (size_t)std::max<int64_t>(count, 1) * sizeof(T));
+    hipError_t e = ek_dev_malloc((void **)dst, (size_t)std::max<int64_t>(count, 1) * sizeof(T));
     if (e == hipSuccess && count > 0)
         e = hipMemcpyAsync(*dst, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice, s);
     return e;
@@ -302,7 +302,7 @@ extern "C" int ek_msm_mle_prinz(int device, int32_t n, int64_t n_pairs, int32_t 
             return ek_set_error(EK_EHIP, "hipSetDevice(%d): %s", device,
                                 hipGetErrorString(e0));
     }
-    MLE_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    MLE_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
     MLE_HIP(mle_upload(&d_lp, level_ptr, (int64_t)n_levels + 1, s));
     MLE_HIP(mle_upload(&d_pi, pair_i, n_pairs, s));
     MLE_HIP(mle_upload(&d_pj, pair_j, n_pairs, s));
@@ -313,7 +313,7 @@ extern "C" int ek_msm_mle_prinz(int device, int32_t n, int64_t n_pairs, int32_t 
     MLE_HIP(mle_upload(&d_xp, (const double *)x_pairs, n_pairs, s));
     MLE_HIP(mle_upload(&d_xd, (const double *)x_diag, (int64_t)n, s));
     MLE_HIP(mle_upload(&d_xrs, (const double *)x_rs, (int64_t)n, s));
-    MLE_HIP(hipMalloc((void **)&d_out, sizeof(MleOut)));
+    MLE_HIP(ek_dev_malloc((void **)&d_out, sizeof(MleOut)));
     if (in_lds) {
         if (lds > 48 * 1024)
             MLE_HIP(hipFuncSetAttribute((const void *)msm_mle_prinz_kernel<true>,
@@ -342,18 +342,18 @@ extern "C" int ek_msm_mle_prinz(int device, int32_t n, int64_t n_pairs, int32_t 
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_lp);
-    (void)hipFree(d_pi);
-    (void)hipFree(d_pj);
-    (void)hipFree(d_cij);
-    (void)hipFree(d_cji);
-    (void)hipFree(d_cd);
-    (void)hipFree(d_crs);
-    (void)hipFree(d_xp);
-    (void)hipFree(d_xd);
-    (void)hipFree(d_xrs);
-    (void)hipFree(d_out);
+    (void)ek_dev_free(d_lp);
+    (void)ek_dev_free(d_pi);
+    (void)ek_dev_free(d_pj);
+    (void)ek_dev_free(d_cij);
+    (void)ek_dev_free(d_cji);
+    (void)ek_dev_free(d_cd);
+    (void)ek_dev_free(d_crs);
+    (void)ek_dev_free(d_xp);
+    (void)ek_dev_free(d_xd);
+    (void)ek_dev_free(d_xrs);
+    (void)ek_dev_free(d_out);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }

@@ -95,16 +95,16 @@ struct PockDev {
 
 static void pock_dev_free(PockDev &d)
 {
-    (void)hipFree(d.xyz);
-    (void)hipFree(d.fr);
-    (void)hipFree(d.touch);
-    (void)hipFree(d.rank);
-    (void)hipFree(d.ext);
-    (void)hipFree(d.parent);
-    (void)hipFree(d.bcnt);
-    (void)hipFree(d.boff);
-    (void)hipFree(d.total);
-    (void)hipFree(d.out);
+    (void)ek_dev_free(d.xyz);
+    (void)ek_dev_free(d.fr);
+    (void)ek_dev_free(d.touch);
+    (void)ek_dev_free(d.rank);
+    (void)ek_dev_free(d.ext);
+    (void)ek_dev_free(d.parent);
+    (void)ek_dev_free(d.bcnt);
+    (void)ek_dev_free(d.boff);
+    (void)ek_dev_free(d.total);
+    (void)ek_dev_free(d.out);
     d = PockDev();
 }
 
@@ -546,9 +546,9 @@ static int pock_upload_cutoffs(const double *cutoff, int32_t atoms, double **d_c
     for (int32_t i = 0; i < atoms; ++i)
         sq[i] = cutoff[i] * cutoff[i];
     int rc = EK_OK;
-    hipError_t e = hipMalloc((void **)d_c, (size_t)atoms * sizeof(double));
+    hipError_t e = ek_dev_malloc((void **)d_c, (size_t)atoms * sizeof(double));
     if (e == hipSuccess)
-        e = hipMalloc((void **)d_c2, (size_t)atoms * sizeof(double));
+        e = ek_dev_malloc((void **)d_c2, (size_t)atoms * sizeof(double));
     if (e == hipSuccess)
         e = hipMemcpyAsync(*d_c, cutoff, (size_t)atoms * sizeof(double), hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
@@ -578,13 +578,13 @@ extern "C" int ek_pockets_close(ek_pockets *h)
     (void)hipSetDevice(h->device);
     if (h->s)
         (void)hipStreamSynchronize(h->s);
-    (void)hipFree(h->cutoff);
-    (void)hipFree(h->cutoff2);
+    (void)ek_dev_free(h->cutoff);
+    (void)ek_dev_free(h->cutoff2);
     for (hipEvent_t e : h->ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (h->s)
-        (void)hipStreamDestroy(h->s);
+        (void)ek_stream_destroy(h->s);
     pock_drop_result(h);
     delete h;
     return EK_OK;
@@ -592,9 +592,9 @@ extern "C" int ek_pockets_close(ek_pockets *h)
 
 static int pock_open(ek_pockets *h, const double *cutoff)
 {
-    POCK_TRY(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+    POCK_TRY(ek_stream_create_flags(&h->s, hipStreamNonBlocking));
     for (hipEvent_t &e : h->ev)
-        POCK_TRY(hipEventCreate(&e));
+        POCK_TRY(ek_event_create(&e));
     return pock_upload_cutoffs(cutoff, h->atoms, &h->cutoff, &h->cutoff2, h->s);
 }
 
@@ -639,10 +639,10 @@ static int pock_grow_out(PockDev &d, size_t n)
 {
     if (n <= d.out_cap)
         return EK_OK;
-    (void)hipFree(d.out);
+    (void)ek_dev_free(d.out);
     d.out = nullptr;
     d.out_cap = 0;
-    POCK_TRY(hipMalloc((void **)&d.out, 2 * n * sizeof(int32_t)));
+    POCK_TRY(ek_dev_malloc((void **)&d.out, 2 * n * sizeof(int32_t)));
     d.out_cap = n;
     return EK_OK;
 }
@@ -775,24 +775,24 @@ static int pock_run(ek_pockets *h, PockDev &d, const float *xyz, int64_t frames,
     if (!host_out)
         return ek_set_error(EK_ENOMEM, "ek_pockets_run: out of host memory");
     const size_t nbk = (size_t)max_cells / POCK_WG + 1;
-    hipError_t e = hipMalloc((void **)&d.xyz, (size_t)max_nf * h->atoms * 3 * sizeof(float));
+    hipError_t e = ek_dev_malloc((void **)&d.xyz, (size_t)max_nf * h->atoms * 3 * sizeof(float));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&d.fr, (size_t)max_nf * sizeof(PockFrame));
+        e = ek_dev_malloc((void **)&d.fr, (size_t)max_nf * sizeof(PockFrame));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&d.touch, (size_t)max_cells + 1);
+        e = ek_dev_malloc((void **)&d.touch, (size_t)max_cells + 1);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&d.parent, ((size_t)max_cells + 1) * sizeof(int32_t));
+        e = ek_dev_malloc((void **)&d.parent, ((size_t)max_cells + 1) * sizeof(int32_t));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&d.ext, ((size_t)max_lines + 1) * sizeof(uint32_t));
+        e = ek_dev_malloc((void **)&d.ext, ((size_t)max_lines + 1) * sizeof(uint32_t));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&d.bcnt, nbk * sizeof(int32_t));
+        e = ek_dev_malloc((void **)&d.bcnt, nbk * sizeof(int32_t));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&d.boff, nbk * sizeof(int32_t));
+        e = ek_dev_malloc((void **)&d.boff, nbk * sizeof(int32_t));
     if (e == hipSuccess)
-        e = hipMalloc((void **)&d.total, sizeof(int32_t));
+        e = ek_dev_malloc((void **)&d.total, sizeof(int32_t));
     if (e != hipSuccess)
         rc = ek_set_error(e == hipErrorOutOfMemory ? EK_ENOMEM : EK_EHIP,
-                          "ek_pockets_run: hipMalloc: %s", hipGetErrorString(e));
+                          "ek_pockets_run: ek_dev_malloc: %s", hipGetErrorString(e));
     for (int64_t i = 0, f0 = 0; rc == EK_OK && i < n_chunks; f0 = chunk_end[i++]) {
         const int64_t nf = chunk_end[i] - f0;
         PockShape sh;
@@ -909,9 +909,9 @@ static int pock_touches(PockDev &d, double **d_c, double **d_c2, const float *xy
                         const double *cutoff, double spacing, const PockFrame &fr,
                         const PockShape &sh, uint8_t *out)
 {
-    POCK_TRY(hipMalloc((void **)&d.xyz, (size_t)atoms * 3 * sizeof(float)));
-    POCK_TRY(hipMalloc((void **)&d.fr, sizeof(PockFrame)));
-    POCK_TRY(hipMalloc((void **)&d.touch, (size_t)sh.cells));
+    POCK_TRY(ek_dev_malloc((void **)&d.xyz, (size_t)atoms * 3 * sizeof(float)));
+    POCK_TRY(ek_dev_malloc((void **)&d.fr, sizeof(PockFrame)));
+    POCK_TRY(ek_dev_malloc((void **)&d.touch, (size_t)sh.cells));
     int rc = pock_upload_cutoffs(cutoff, atoms, d_c, d_c2, nullptr);
     if (rc != EK_OK)
         return rc;
@@ -951,8 +951,8 @@ extern "C" int ek_pockets_touches(int device, const float *xyz, int32_t atoms,
     double *d_c = nullptr, *d_c2 = nullptr;
     rc = pock_touches(d, &d_c, &d_c2, xyz, atoms, cutoff, spacing, fr, sh, touches_out);
     (void)hipDeviceSynchronize();
-    (void)hipFree(d_c);
-    (void)hipFree(d_c2);
+    (void)ek_dev_free(d_c);
+    (void)ek_dev_free(d_c2);
     pock_dev_free(d);
     return rc;
 }
@@ -960,10 +960,10 @@ extern "C" int ek_pockets_touches(int device, const float *xyz, int32_t atoms,
 static int pock_ranks(PockDev &d, const uint8_t *touches, const PockFrame &fr, const PockShape &sh,
                       uint8_t *out)
 {
-    POCK_TRY(hipMalloc((void **)&d.fr, sizeof(PockFrame)));
-    POCK_TRY(hipMalloc((void **)&d.touch, (size_t)sh.cells));
-    POCK_TRY(hipMalloc((void **)&d.rank, (size_t)sh.cells));
-    POCK_TRY(hipMalloc((void **)&d.ext, (size_t)sh.lines * sizeof(uint32_t)));
+    POCK_TRY(ek_dev_malloc((void **)&d.fr, sizeof(PockFrame)));
+    POCK_TRY(ek_dev_malloc((void **)&d.touch, (size_t)sh.cells));
+    POCK_TRY(ek_dev_malloc((void **)&d.rank, (size_t)sh.cells));
+    POCK_TRY(ek_dev_malloc((void **)&d.ext, (size_t)sh.lines * sizeof(uint32_t)));
     POCK_TRY(hipMemcpy(d.fr, &fr, sizeof(PockFrame), hipMemcpyHostToDevice));
     POCK_TRY(hipMemcpy(d.touch, touches, (size_t)sh.cells, hipMemcpyHostToDevice));
     pock_launch_rank(d, 1, sh, 0, d.rank, nullptr, nullptr);
@@ -992,9 +992,9 @@ extern "C" int ek_pockets_ranks(int device, const uint8_t *touches, const int32_
 static int pock_labels(PockDev &d, const uint8_t *mask, const PockFrame &fr, const PockShape &sh,
                        int32_t *out)
 {
-    POCK_TRY(hipMalloc((void **)&d.fr, sizeof(PockFrame)));
-    POCK_TRY(hipMalloc((void **)&d.touch, (size_t)sh.cells));
-    POCK_TRY(hipMalloc((void **)&d.parent, (size_t)sh.cells * sizeof(int32_t)));
+    POCK_TRY(ek_dev_malloc((void **)&d.fr, sizeof(PockFrame)));
+    POCK_TRY(ek_dev_malloc((void **)&d.touch, (size_t)sh.cells));
+    POCK_TRY(ek_dev_malloc((void **)&d.parent, (size_t)sh.cells * sizeof(int32_t)));
     POCK_TRY(hipMemcpy(d.fr, &fr, sizeof(PockFrame), hipMemcpyHostToDevice));
     POCK_TRY(hipMemcpy(d.touch, mask, (size_t)sh.cells, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(pock_mask_kernel, dim3(pock_blocks(sh.cells)), dim3(POCK_WG), 0, nullptr,

@@ -366,24 +366,24 @@ static int rt_run(const char *who, int device, const float *angles, const float 
     rc = rt_check_memory(in_b + ang_b + st_b + map_b + (size_t)n * 20, who);
     if (rc != EK_OK)
         goto done;
-    RT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    RT_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
     for (hipEvent_t &e : ev)
-        RT_HIP(hipEventCreate(&e));
-    RT_HIP(hipMalloc((void **)&d_in, in_b));
+        RT_HIP(ek_event_create(&e));
+    RT_HIP(ek_dev_malloc((void **)&d_in, in_b));
     RT_HIP(hipMemcpyAsync(d_in, from_xyz ? xyz : angles, in_b, hipMemcpyHostToDevice, s));
     if (from_xyz) {
-        RT_HIP(hipMalloc((void **)&d_quads, (size_t)n * 4 * sizeof(int32_t)));
+        RT_HIP(ek_dev_malloc((void **)&d_quads, (size_t)n * 4 * sizeof(int32_t)));
         RT_HIP(hipMemcpyAsync(d_quads, quads, (size_t)n * 4 * sizeof(int32_t),
                               hipMemcpyHostToDevice, s));
         if (angles_out)
-            RT_HIP(hipMalloc((void **)&d_ang, ang_b));
+            RT_HIP(ek_dev_malloc((void **)&d_ang, ang_b));
     }
     if (states_out) {
-        RT_HIP(hipMalloc((void **)&d_kind, (size_t)n));
-        RT_HIP(hipMalloc((void **)&d_kinds, (size_t)n_kinds * sizeof(rt_kind)));
-        RT_HIP(hipMalloc((void **)&d_maps, (size_t)chunks * n * sizeof(uint32_t)));
-        RT_HIP(hipMalloc((void **)&d_start, (size_t)chunks * n));
-        RT_HIP(hipMalloc((void **)&d_states, st_b));
+        RT_HIP(ek_dev_malloc((void **)&d_kind, (size_t)n));
+        RT_HIP(ek_dev_malloc((void **)&d_kinds, (size_t)n_kinds * sizeof(rt_kind)));
+        RT_HIP(ek_dev_malloc((void **)&d_maps, (size_t)chunks * n * sizeof(uint32_t)));
+        RT_HIP(ek_dev_malloc((void **)&d_start, (size_t)chunks * n));
+        RT_HIP(ek_dev_malloc((void **)&d_states, st_b));
         RT_HIP(hipMemcpyAsync(d_kind, kind, (size_t)n, hipMemcpyHostToDevice, s));
         RT_HIP(hipMemcpyAsync(d_kinds, kinds, (size_t)n_kinds * sizeof(rt_kind),
                               hipMemcpyHostToDevice, s));
@@ -438,19 +438,19 @@ static int rt_run(const char *who, int device, const float *angles, const float 
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_in);
-    (void)hipFree(d_ang);
-    (void)hipFree(d_quads);
-    (void)hipFree(d_kind);
-    (void)hipFree(d_kinds);
-    (void)hipFree(d_maps);
-    (void)hipFree(d_start);
-    (void)hipFree(d_states);
+    (void)ek_dev_free(d_in);
+    (void)ek_dev_free(d_ang);
+    (void)ek_dev_free(d_quads);
+    (void)ek_dev_free(d_kind);
+    (void)ek_dev_free(d_kinds);
+    (void)ek_dev_free(d_maps);
+    (void)ek_dev_free(d_start);
+    (void)ek_dev_free(d_states);
     for (hipEvent_t e : ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     delete[] kinds;
     return rc;
 }

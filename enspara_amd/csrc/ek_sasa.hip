@@ -194,16 +194,16 @@ extern "C" int ek_sasa_close(ek_sasa *h)
     (void)hipSetDevice(h->device);
     if (h->s)
         (void)hipStreamSynchronize(h->s);
-    (void)hipFree(h->R);
-    (void)hipFree(h->R2);
-    (void)hipFree(h->sp);
-    (void)hipFree(h->goff);
-    (void)hipFree(h->gidx);
+    (void)ek_dev_free(h->R);
+    (void)ek_dev_free(h->R2);
+    (void)ek_dev_free(h->sp);
+    (void)ek_dev_free(h->goff);
+    (void)ek_dev_free(h->gidx);
     for (hipEvent_t e : h->ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (h->s)
-        (void)hipStreamDestroy(h->s);
+        (void)ek_stream_destroy(h->s);
     delete h;
     return EK_OK;
 }
@@ -260,20 +260,20 @@ extern "C" int ek_sasa_open(int device, int32_t atoms, const float *R, int32_t n
     for (int32_t k = 0; k < n_points; ++k)
         for (int d = 0; d < 3; ++d)
             tmp[(size_t)atoms + (size_t)d * n_points + k] = points[3 * (size_t)k + d];
-    SASA_HIP(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+    SASA_HIP(ek_stream_create_flags(&h->s, hipStreamNonBlocking));
     for (hipEvent_t &e : h->ev)
-        SASA_HIP(hipEventCreate(&e));
-    SASA_HIP(hipMalloc((void **)&h->R, (size_t)atoms * sizeof(float)));
-    SASA_HIP(hipMalloc((void **)&h->R2, (size_t)atoms * sizeof(float)));
-    SASA_HIP(hipMalloc((void **)&h->sp, 3 * (size_t)n_points * sizeof(float)));
+        SASA_HIP(ek_event_create(&e));
+    SASA_HIP(ek_dev_malloc((void **)&h->R, (size_t)atoms * sizeof(float)));
+    SASA_HIP(ek_dev_malloc((void **)&h->R2, (size_t)atoms * sizeof(float)));
+    SASA_HIP(ek_dev_malloc((void **)&h->sp, 3 * (size_t)n_points * sizeof(float)));
     SASA_HIP(hipMemcpyAsync(h->R, R, (size_t)atoms * sizeof(float), hipMemcpyHostToDevice, h->s));
     SASA_HIP(hipMemcpyAsync(h->R2, tmp, (size_t)atoms * sizeof(float), hipMemcpyHostToDevice,
                             h->s));
     SASA_HIP(hipMemcpyAsync(h->sp, tmp + atoms, 3 * (size_t)n_points * sizeof(float),
                             hipMemcpyHostToDevice, h->s));
     if (n_groups > 0) {
-        SASA_HIP(hipMalloc((void **)&h->goff, ((size_t)n_groups + 1) * sizeof(int32_t)));
-        SASA_HIP(hipMalloc((void **)&h->gidx, (size_t)n_idx * sizeof(int32_t)));
+        SASA_HIP(ek_dev_malloc((void **)&h->goff, ((size_t)n_groups + 1) * sizeof(int32_t)));
+        SASA_HIP(ek_dev_malloc((void **)&h->gidx, (size_t)n_idx * sizeof(int32_t)));
         SASA_HIP(hipMemcpyAsync(h->goff, group_offsets, ((size_t)n_groups + 1) * sizeof(int32_t),
                                 hipMemcpyHostToDevice, h->s));
         SASA_HIP(hipMemcpyAsync(h->gidx, group_atoms, (size_t)n_idx * sizeof(int32_t),
@@ -333,11 +333,11 @@ extern "C" int ek_sasa_run(ek_sasa *h, const float *xyz, int64_t frames, int64_t
 
     float *d_xyz = nullptr, *d_areas = nullptr, *d_groups = nullptr;
     int32_t *d_counts = nullptr;
-    SASA_HIP(hipMalloc((void **)&d_xyz, (size_t)chunk * h->atoms * 3 * sizeof(float)));
-    SASA_HIP(hipMalloc((void **)&d_counts, (size_t)chunk * h->atoms * sizeof(int32_t)));
-    SASA_HIP(hipMalloc((void **)&d_areas, (size_t)chunk * h->atoms * sizeof(float)));
+    SASA_HIP(ek_dev_malloc((void **)&d_xyz, (size_t)chunk * h->atoms * 3 * sizeof(float)));
+    SASA_HIP(ek_dev_malloc((void **)&d_counts, (size_t)chunk * h->atoms * sizeof(int32_t)));
+    SASA_HIP(ek_dev_malloc((void **)&d_areas, (size_t)chunk * h->atoms * sizeof(float)));
     if (groups_out)
-        SASA_HIP(hipMalloc((void **)&d_groups, (size_t)chunk * h->n_groups * sizeof(float)));
+        SASA_HIP(ek_dev_malloc((void **)&d_groups, (size_t)chunk * h->n_groups * sizeof(float)));
     for (int64_t f0 = 0; f0 < frames; f0 += chunk) {
         const int64_t nf = (frames - f0 < chunk) ? frames - f0 : chunk;
         const size_t cells = (size_t)nf * h->atoms;
@@ -375,10 +375,10 @@ extern "C" int ek_sasa_run(ek_sasa *h, const float *xyz, int64_t frames, int64_t
     }
 done:
     (void)hipStreamSynchronize(h->s);
-    (void)hipFree(d_xyz);
-    (void)hipFree(d_counts);
-    (void)hipFree(d_areas);
-    (void)hipFree(d_groups);
+    (void)ek_dev_free(d_xyz);
+    (void)ek_dev_free(d_counts);
+    (void)ek_dev_free(d_areas);
+    (void)ek_dev_free(d_groups);
     return rc;
 }
 

@@ -248,22 +248,22 @@ static int tpt_run(const char *who, int mode, int device, int32_t n, const doubl
         delete[] h_role;
         return rc;
     }
-    TPT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    TPT_HIP(hipMalloc((void **)&d_T, nn * sizeof(double)));
-    TPT_HIP(hipMalloc((void **)&d_aug, (size_t)npad * ld * sizeof(double)));
-    TPT_HIP(hipMalloc((void **)&d_piv, (size_t)npad * sizeof(int32_t)));
-    TPT_HIP(hipMalloc((void **)&d_status, sizeof(int32_t)));
-    TPT_HIP(hipMalloc((void **)&d_vec, (size_t)n * sizeof(double)));
+    TPT_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
+    TPT_HIP(ek_dev_malloc((void **)&d_T, nn * sizeof(double)));
+    TPT_HIP(ek_dev_malloc((void **)&d_aug, (size_t)npad * ld * sizeof(double)));
+    TPT_HIP(ek_dev_malloc((void **)&d_piv, (size_t)npad * sizeof(int32_t)));
+    TPT_HIP(ek_dev_malloc((void **)&d_status, sizeof(int32_t)));
+    TPT_HIP(ek_dev_malloc((void **)&d_vec, (size_t)n * sizeof(double)));
     TPT_HIP(hipMemcpyAsync(d_T, T, nn * sizeof(double), hipMemcpyHostToDevice, s));
     TPT_HIP(hipMemsetAsync(d_status, 0xff, sizeof(int32_t), s));
     if (pops) {
-        TPT_HIP(hipMalloc((void **)&d_pi, (size_t)n * sizeof(double)));
+        TPT_HIP(ek_dev_malloc((void **)&d_pi, (size_t)n * sizeof(double)));
         TPT_HIP(hipMemcpyAsync(d_pi, pops, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
                                s));
     }
     if (!all) {
-        TPT_HIP(hipMalloc((void **)&d_role, (size_t)n * sizeof(int32_t)));
-        TPT_HIP(hipMalloc((void **)&d_sinks, (size_t)n_sinks * sizeof(int32_t)));
+        TPT_HIP(ek_dev_malloc((void **)&d_role, (size_t)n * sizeof(int32_t)));
+        TPT_HIP(ek_dev_malloc((void **)&d_sinks, (size_t)n_sinks * sizeof(int32_t)));
         TPT_HIP(hipMemcpyAsync(d_role, h_role, (size_t)n * sizeof(int32_t),
                                hipMemcpyHostToDevice, s));
         TPT_HIP(hipMemcpyAsync(d_sinks, sinks, (size_t)n_sinks * sizeof(int32_t),
@@ -301,16 +301,16 @@ static int tpt_run(const char *who, int mode, int device, int32_t n, const doubl
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_T);
-    (void)hipFree(d_aug);
-    (void)hipFree(d_pi);
-    (void)hipFree(d_vec);
-    (void)hipFree(d_role);
-    (void)hipFree(d_sinks);
-    (void)hipFree(d_piv);
-    (void)hipFree(d_status);
+    (void)ek_dev_free(d_T);
+    (void)ek_dev_free(d_aug);
+    (void)ek_dev_free(d_pi);
+    (void)ek_dev_free(d_vec);
+    (void)ek_dev_free(d_role);
+    (void)ek_dev_free(d_sinks);
+    (void)ek_dev_free(d_piv);
+    (void)ek_dev_free(d_status);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     delete[] h_role;
     return rc;
 }
@@ -369,10 +369,10 @@ extern "C" int ek_lu_solve(int device, int32_t n, const double *A, int32_t nrhs,
     rc = tpt_check_memory(((size_t)npad * ld + (size_t)npad) * sizeof(double), "ek_lu_solve");
     if (rc != EK_OK)
         return rc;
-    TPT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    TPT_HIP(hipMalloc((void **)&d_aug, (size_t)npad * ld * sizeof(double)));
-    TPT_HIP(hipMalloc((void **)&d_piv, (size_t)npad * sizeof(int32_t)));
-    TPT_HIP(hipMalloc((void **)&d_status, sizeof(int32_t)));
+    TPT_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
+    TPT_HIP(ek_dev_malloc((void **)&d_aug, (size_t)npad * ld * sizeof(double)));
+    TPT_HIP(ek_dev_malloc((void **)&d_piv, (size_t)npad * sizeof(int32_t)));
+    TPT_HIP(ek_dev_malloc((void **)&d_status, sizeof(int32_t)));
     TPT_HIP(hipMemsetAsync(d_status, 0xff, sizeof(int32_t), s));
     TPT_HIP(hipMemcpy2DAsync(d_aug, ld * sizeof(double), A, (size_t)n * sizeof(double),
                              (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, s));
@@ -396,10 +396,10 @@ extern "C" int ek_lu_solve(int device, int32_t n, const double *A, int32_t nrhs,
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_aug);
-    (void)hipFree(d_piv);
-    (void)hipFree(d_status);
+    (void)ek_dev_free(d_aug);
+    (void)ek_dev_free(d_piv);
+    (void)ek_dev_free(d_status);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }

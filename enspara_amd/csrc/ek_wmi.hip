@@ -222,15 +222,15 @@ extern "C" int ek_wmi_run(int device, const uint8_t *codes, const double *weight
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float ms = 0.f;
     const unsigned blocks = (unsigned)((M + WMI_BLOCK - 1) / WMI_BLOCK);
-    WMI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    WMI_HIP(ek_stream_create_flags(&s, hipStreamNonBlocking));
     for (hipEvent_t &e : ev)
-        WMI_HIP(hipEventCreate(&e));
-    WMI_HIP(hipMalloc((void **)&d_raw, raw_b));
-    WMI_HIP(hipMalloc((void **)&d_codes, code_b));
-    WMI_HIP(hipMalloc((void **)&d_w, w_b));
-    WMI_HIP(hipMalloc((void **)&d_part, part_b));
-    WMI_HIP(hipMalloc((void **)&d_P, P_b));
-    WMI_HIP(hipMalloc((void **)&d_mi, mi_b));
+        WMI_HIP(ek_event_create(&e));
+    WMI_HIP(ek_dev_malloc((void **)&d_raw, raw_b));
+    WMI_HIP(ek_dev_malloc((void **)&d_codes, code_b));
+    WMI_HIP(ek_dev_malloc((void **)&d_w, w_b));
+    WMI_HIP(ek_dev_malloc((void **)&d_part, part_b));
+    WMI_HIP(ek_dev_malloc((void **)&d_P, P_b));
+    WMI_HIP(ek_dev_malloc((void **)&d_mi, mi_b));
     WMI_HIP(hipEventRecord(ev[0], s));
     WMI_HIP(hipMemcpyAsync(d_raw, codes, raw_b, hipMemcpyHostToDevice, s));
     WMI_HIP(hipMemsetAsync(d_w, 0, w_b, s));
@@ -262,17 +262,17 @@ extern "C" int ek_wmi_run(int device, const uint8_t *codes, const double *weight
 done:
     if (s)
         (void)hipStreamSynchronize(s);
-    (void)hipFree(d_raw);
-    (void)hipFree(d_codes);
-    (void)hipFree(d_w);
-    (void)hipFree(d_part);
-    (void)hipFree(d_P);
-    (void)hipFree(d_mi);
+    (void)ek_dev_free(d_raw);
+    (void)ek_dev_free(d_codes);
+    (void)ek_dev_free(d_w);
+    (void)ek_dev_free(d_part);
+    (void)ek_dev_free(d_P);
+    (void)ek_dev_free(d_mi);
     for (hipEvent_t e : ev)
         if (e)
-            (void)hipEventDestroy(e);
+            (void)ek_event_destroy(e);
     if (s)
-        (void)hipStreamDestroy(s);
+        (void)ek_stream_destroy(s);
     return rc;
 }
 

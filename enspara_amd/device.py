@@ -83,7 +83,11 @@ class FrameStore:
     def from_array(cls, X, device=0, global_offset=0, stream=None):
         xyz = as_xyz(X)
         st = cls(xyz.shape[0], xyz.shape[1], device, global_offset, stream)
-        st.load(xyz)
+        try:
+            st.load(xyz)
+        except BaseException:       # (nobody gets the store: give the context back now)
+            st.close()
+            raise
         return st
 
     # -- data ---------------------------------------------------------------

@@ -55,8 +55,13 @@ class _Resident:
         _lib.check(self.L.ek_feat_create(int(device), Xc.shape[0], Xc.shape[1],
                                          kind, C.byref(h)))
         self._h = h
-        _lib.check(self.L.ek_feat_load(self._h, Xc.ctypes.data_as(C.c_void_p),
-                                       0, Xc.shape[0]))
+        try:
+            _lib.check(self.L.ek_feat_load(self._h, Xc.ctypes.data_as(C.c_void_p),
+                                           0, Xc.shape[0]))
+        except BaseException:       # (nobody gets the object: give the handle back now)
+            self.L.ek_feat_destroy(self._h)
+            self._h = None
+            raise
 
     def distance(self, metric, yc, out):
         _lib.check(self.L.ek_feat_distance(
@@ -110,11 +115,14 @@ class _Resident:
             C.byref(st)))
         return st.value, c.value, p.value
 
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.ek_feat_destroy(self._h)
+            self._h = None
+
     def __del__(self):
         try:
-            if self._h:
-                self.L.ek_feat_destroy(self._h)
-                self._h = None
+            self.close()
         except Exception:
             pass
 
@@ -140,9 +148,13 @@ class FeatureStore(_Resident):
             self.device, self.n, self.F, self.kind, self.global_offset,
             C.c_void_p(int(stream) if stream else None), C.byref(h)))
         self._h = h
-        _lib.check(self.L.ek_feat_load(
-            self._h, Xc.ctypes.data_as(C.c_void_p) if self.n else None, 0,
-            self.n))
+        try:
+            _lib.check(self.L.ek_feat_load(
+                self._h, Xc.ctypes.data_as(C.c_void_p) if self.n else None, 0,
+                self.n))
+        except BaseException:       # (nobody gets the object: give the handle back now)
+            self.close()
+            raise
         self.record_bytes = int(self.L.ek_feat_record_bytes(self.F, self.kind))
         self.dtype = Xc.dtype
 
@@ -349,7 +361,10 @@ def _run(metric, X, y, out, device):
     dt = _working_dtype(X, metric == 2)
     res = _Resident(np.ascontiguousarray(X, dtype=dt),
                     _KIND[np.dtype(dt).name], device)
-    res.distance(metric, np.ascontiguousarray(y, dtype=dt), out)
+    try:        # (not left to __del__: a raise keeps this frame, and the handle, alive)
+        res.distance(metric, np.ascontiguousarray(y, dtype=dt), out)
+    finally:
+        res.close()
     return out
 
 
@@ -397,7 +412,10 @@ def kcenters_resident(X, metric_id, first_label, max_new, cutoff, distances,
                     _KIND[np.dtype(dt).name], device)
     d = np.ascontiguousarray(distances, dtype=np.float64).copy()
     a = np.ascontiguousarray(assignments, dtype=np.int32).copy()
-    centers, fmax = res.kcenters(metric_id, first_label, max_new, cutoff, d, a)
+    try:
+        centers, fmax = res.kcenters(metric_id, first_label, max_new, cutoff, d, a)
+    finally:
+        res.close()
     return centers, d, a.astype(np.asarray(assignments).dtype), fmax
 
 
@@ -418,5 +436,8 @@ def assign_nearest_resident(X, metric_id, centers, device=0):
         return np.zeros(0, dtype=np.int64), np.full(0, np.inf)
     res = _Resident(np.ascontiguousarray(Xa, dtype=dt),
                     _KIND[np.dtype(dt).name], device)
-    d, a = res.assign_nearest(metric_id, c)
+    try:
+        d, a = res.assign_nearest(metric_id, c)
+    finally:
+        res.close()
     return a.astype(np.int64), d

@@ -1324,6 +1324,22 @@ int ek_qcp_probe(int device, const float *S, const double *Gx, const double *Gy,
  * stderr), 0 without EK_POISON. */
 int ek_debug_guards(ek_ctx *ctx);
 
+/* ---- what the library holds on the device ------------------------------------
+ * Every device allocation, pinned host allocation, stream and event of the library
+ * goes through one counted front (csrc/ek_track.h).  out[7], all counted inside the
+ * library (other processes on the card do not move them):
+ *   [0] live device allocations        [1] their bytes (as asked for)
+ *   [2] live pinned host allocations   [3] their bytes
+ *   [4] live streams                   [5] live events
+ *   [6] device allocations that succeeded since the library was loaded (monotonic)
+ * Works without a device (all zeros there).  Always returns EK_OK for out != NULL. */
+int ek_live_resources(int64_t *out);
+/* TEST AID.  Arms one failure: the k-th device allocation from now (0-based, all
+ * threads, whatever the device) returns hipErrorOutOfMemory from the counted front
+ * without calling HIP or touching the device; the arm is then clear again.  k < 0
+ * disarms.  Returns the arm that was pending (-1: none). */
+int64_t ek_fail_alloc_at(int64_t k);
+
 #ifdef __cplusplus
 }
 #endif

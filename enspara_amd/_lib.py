@@ -82,7 +82,7 @@ SYMBOLS = [
     "ek_reserve_centers",
     "ek_debug_guards",
     "ek_timing_begin", "ek_timing_end", "ek_timing_form", "ek_hbm_copy_rate",
-    "ek_qcp_probe",
+    "ek_qcp_probe", "ek_pam_pairs_probe",
     "ek_live_resources", "ek_fail_alloc_at",
 ]
 
@@ -363,6 +363,8 @@ def load():
     L.ek_timing_form.argtypes = [vp, i32p]
     L.ek_hbm_copy_rate.argtypes = [C.c_int, C.c_size_t, f64p]
     L.ek_qcp_probe.argtypes = [C.c_int, vp, vp, vp, i32, vp, C.c_int64, vp, vp, vp]
+    L.ek_pam_pairs_probe.argtypes = [C.c_int, i32, i32, vp, vp, i64, vp, vp, i32, i32, i32,
+                                     i32, i32, vp, vp, vp, vp, vp, i64, i64, vp]
     L.ek_live_resources.argtypes = [i64p]
     L.ek_fail_alloc_at.argtypes = [i64]
     L.ek_fail_alloc_at.restype = i64

@@ -1573,3 +1573,121 @@ extern "C" int ek_pam_prefetch_stats(ek_ctx *c, int64_t *hits, int64_t *misses)
     return EK_OK;
 }
 
+
+// ---- the window's distance kernels on the caller's arrays (tests) -----------------------
+// The shipped launchers ek_launch_pam_tables / ek_launch_pam_list_dist on host arrays:
+// rows [n_rows][3A] (centred) with their traces, columns [n_col][3A] made into records
+// here.  list == NULL: the tables of a window (rows: the medoid table [K + 1], row K the
+// held medoid); else the listed rows against the columns.  Every output array is copied
+// in before the launch and out after it, so the caller's prefill shows what no kernel
+// wrote.  One device allocation; the form of the pairs kernels is the caller's for the
+// length of the call.
+extern "C" int ek_pam_pairs_probe(int device, int32_t form, int32_t n_atoms,
+                                  const float *rows, const double *rows_G, int64_t n_rows,
+                                  const float *cols, const double *cols_G, int32_t n_col,
+                                  int32_t K, int32_t held, int32_t old_lo, int32_t n_old,
+                                  const float *dprop, float *T, float *O, float *dmin,
+                                  const uint32_t *list, int64_t n_list, int64_t n_pad,
+                                  float *vecs)
+{
+    const int A = n_atoms;
+    if (!rows || !rows_G || n_rows < 1 || n_rows > ((int64_t)1 << 24) || A < 1 ||
+        A > EK_MAX_ATOMS || n_col < 0 || n_col > EK_PAM_WIN || (n_col > 0 && (!cols || !cols_G)))
+        return ek_fail(EK_EARG, "ek_pam_pairs_probe: bad argument");
+    const bool tables = list == nullptr;
+    int n_grp = 0;      // groups of EK_PAM_GROUP columns dmin has
+    if (tables) {
+        if (K < 1 || n_rows != (int64_t)K + 1 || held < -1 || held >= K || old_lo < 0 ||
+            n_old < 0 || n_old > EK_PAM_WIN || old_lo + n_old > K || n_col + n_old < 1 ||
+            (dprop && (n_old != n_col || n_col < 1)) || (n_col > 0 && (!T || !dmin)) ||
+            (n_old > 0 && !O))
+            return ek_fail(EK_EARG, "ek_pam_pairs_probe: tables: K=%d held=%d old=[%d,+%d) "
+                                    "n_col=%d", K, held, old_lo, n_old, n_col);
+        n_grp = (n_col + EK_PAM_GROUP - 1) / EK_PAM_GROUP;
+    } else {
+        if (n_list < 1 || n_list > ((int64_t)1 << 24) || n_col < 1 || n_pad < n_rows ||
+            n_pad > ((int64_t)1 << 24) || !vecs)
+            return ek_fail(EK_EARG, "ek_pam_pairs_probe: list: n_list=%lld n_pad=%lld "
+                                    "n_col=%d", (long long)n_list, (long long)n_pad, n_col);
+        for (int64_t i = 0; i < n_list; ++i)
+            if ((int64_t)list[i] >= n_rows)
+                return ek_fail(EK_EARG, "ek_pam_pairs_probe: list[%lld]=%u outside the %lld "
+                                        "rows", (long long)i, list[i], (long long)n_rows);
+    }
+    // the columns as records
+    const size_t rstride = ek_rec_bytes(A);
+    std::vector<unsigned char> recs((size_t)std::max(n_col, 1) * rstride, 0);
+    for (int j = 0; j < n_col; ++j) {
+        EkRecHdr h = {};
+        h.valid = 1;
+        h.gidx = j;
+        h.trace = cols_G[j];
+        memcpy(recs.data() + (size_t)j * rstride, &h, sizeof(h));
+        memcpy(recs.data() + (size_t)j * rstride + sizeof(h), cols + (size_t)j * 3 * A,
+               (size_t)12 * A);
+    }
+    EK_HIP(hipSetDevice(device));
+    // traces | records | rows | list | dprop | T | O | dmin | vecs, each at a multiple of 16
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t b_G = (size_t)n_rows * 8, b_recs = recs.size(),
+                 b_rows = (size_t)n_rows * 12 * A,
+                 b_list = tables ? 0 : (size_t)n_list * 4,
+                 b_dprop = (tables && dprop) ? (size_t)n_col * 4 : 0,
+                 b_T = tables ? (size_t)n_col * K * 4 : 0,
+                 b_O = tables ? (size_t)n_old * K * 4 : 0,
+                 b_dmin = tables ? (size_t)n_grp * K * 4 : 0,
+                 b_vecs = tables ? 0 : (size_t)n_col * (size_t)n_pad * 4;
+    const size_t off_G = 0, off_recs = off_G + up16(b_G), off_rows = off_recs + up16(b_recs),
+                 off_list = off_rows + up16(b_rows), off_dprop = off_list + up16(b_list),
+                 off_T = off_dprop + up16(b_dprop), off_O = off_T + up16(b_T),
+                 off_dmin = off_O + up16(b_O), off_vecs = off_dmin + up16(b_dmin),
+                 total = off_vecs + up16(b_vecs);
+    unsigned char *buf = nullptr;
+    EK_HIP(ek_dev_malloc((void **)&buf, total));
+    struct Piece {
+        void *host;
+        size_t off, bytes;
+        bool in, out;
+    };
+    const Piece pieces[] = {
+        {(void *)rows_G, off_G, b_G, true, false},
+        {(void *)recs.data(), off_recs, b_recs, true, false},
+        {(void *)rows, off_rows, b_rows, true, false},
+        {(void *)list, off_list, b_list, true, false},
+        {(void *)dprop, off_dprop, b_dprop, true, false},
+        {(void *)T, off_T, b_T, true, true},
+        {(void *)O, off_O, b_O, true, true},
+        {(void *)dmin, off_dmin, b_dmin, true, true},
+        {(void *)vecs, off_vecs, b_vecs, true, true},
+    };
+    hipError_t e = hipSuccess;
+    for (const Piece &q : pieces)
+        if (e == hipSuccess && q.in && q.bytes > 0)
+            e = hipMemcpy(buf + q.off, q.host, q.bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const int saved = ek_pam_pairs_form;
+        ek_pam_pairs_form = form ? 1 : 0;
+        if (tables)
+            ek_launch_pam_tables((const float *)(buf + off_rows), (const double *)(buf + off_G),
+                                 A, K, held, buf + off_recs, n_col, old_lo, n_old,
+                                 (float *)(buf + off_T), (float *)(buf + off_O),
+                                 (float *)(buf + off_dmin), 0,
+                                 dprop ? (const float *)(buf + off_dprop) : nullptr);
+        else
+            ek_launch_pam_list_dist((const float *)(buf + off_rows),
+                                    (const double *)(buf + off_G), A,
+                                    (const uint32_t *)(buf + off_list), n_list,
+                                    buf + off_recs, n_col, (float *)(buf + off_vecs), n_pad, 0);
+        ek_pam_pairs_form = saved;
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    for (const Piece &q : pieces)
+        if (e == hipSuccess && q.out && q.bytes > 0)
+            e = hipMemcpy(q.host, buf + q.off, q.bytes, hipMemcpyDeviceToHost);
+    (void)ek_dev_free(buf);
+    if (e != hipSuccess)
+        return ek_fail(EK_EHIP, "ek_pam_pairs_probe: %s", hipGetErrorString(e));
+    return EK_OK;
+}

@@ -1317,6 +1317,30 @@ int ek_hbm_copy_rate(int device, size_t bytes, double *gbytes_per_s);
 int ek_qcp_probe(int device, const float *S, const double *Gx, const double *Gy,
                  int32_t n_atoms, const float *cur, int64_t m, float *full,
                  float *below, unsigned char *cert);
+/* Test entry: the distance kernels of a large shard's PAM window (csrc/ek_pam.hip:
+ * ek_pam_pairs_kernel / ek_pam_pairs16_kernel, modes 0 and 1) on host arrays, through
+ * the launchers the sweep itself calls.  rows [n_rows][3 n_atoms] f32 are centred
+ * structures and rows_G [n_rows] f64 their traces, cols [n_col][3 n_atoms] / cols_G
+ * likewise (n_col <= 32); the columns are made into records here.  form: 1 the
+ * matrix-core kernels, 0 the LDS-staged ones, for this call only (ek_set_option key 21
+ * is what it was afterwards).
+ *   list == NULL, the tables of a window: rows are the medoid table, n_rows == K + 1,
+ *     row K the medoid that row `held` stands for (held == -1: none).
+ *     T [n_col][K] = rmsd(medoid c, column j); O [n_old][K] = rmsd(medoid c, medoid
+ *     old_lo + i), old_lo + n_old <= K, n_old <= 32; dmin [ceil(n_col / 8)][K] = the
+ *     minimum of T over each group of 8 columns.  dprop [n_col] given (n_old == n_col
+ *     then): only O is computed, T[j][c] = max(O[j][c] - dprop[j], 0) and dmin from it.
+ *   list [n_list] given (every entry < n_rows), the listed rows against the columns:
+ *     vecs[j * n_pad + list[i]] = rmsd(row list[i], column j), n_pad >= n_rows.
+ * T, O, dmin and vecs are copied to the device before the launch and back after it:
+ * an entry no kernel wrote still holds what the caller put there.  Not used by the
+ * product path. */
+int ek_pam_pairs_probe(int device, int32_t form, int32_t n_atoms, const float *rows,
+                       const double *rows_G, int64_t n_rows, const float *cols,
+                       const double *cols_G, int32_t n_col, int32_t K, int32_t held,
+                       int32_t old_lo, int32_t n_old, const float *dprop, float *T,
+                       float *O, float *dmin, const uint32_t *list, int64_t n_list,
+                       int64_t n_pad, float *vecs);
 
 /* DEBUG (tools/fuzz_*.py).  With EK_POISON=1 in the environment when the library starts,
  * every working buffer of a context starts as 0x5a bytes (EK_POISON_BYTE) and is followed by a guard page;

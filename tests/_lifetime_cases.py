@@ -188,6 +188,27 @@ def _(st):
     return a, st.rmsd_to_frame(0)
 
 
+# (ek_pam_pairs_probe, the test entry of the window's distance kernels: one allocation
+# per call, whatever the mode and the form)
+def _pairs_inputs():
+    from oracle import qcp
+    c, G = qcp.center_and_trace(_frames()[:80])
+    return (c[:66], G[:66]), (c[66:], G[66:])
+
+
+@case("ek_pam_pairs_probe: tables, bounds and a list, both forms")
+def _():
+    import _pam_probe as pp
+    (rc, rG), (cc, cG) = _pairs_inputs()
+    dprop = np.linspace(0.0, 0.2, len(cc)).astype(np.float32)
+    out = []
+    for form in (1, 0):
+        out += pp.tables(form, rc, rG, cc, cG, 7, 3, 9)
+        out += pp.tables(form, rc, rG, cc, cG, 7, 3, len(cc), dprop)
+        out.append(pp.listed(form, rc, rG, cc, cG, [65, 3, 40, 4], 70))
+    return out
+
+
 @contextlib.contextmanager
 def _open_frame_shard():
     import torch
@@ -722,6 +743,20 @@ def _():
         _lib.check(L.ek_sasa_run(h, None, 2, 1, None, None, None))
     finally:
         L.ek_sasa_close(h)
+
+
+@raises("ek_pam_pairs_probe with a list entry past the rows", _lib.HipError)
+def _():
+    import _pam_probe as pp
+    (rc, rG), (cc, cG) = _pairs_inputs()
+    pp.listed(1, rc, rG, cc, cG, [65, 66], 70)
+
+
+@raises("ek_pam_pairs_probe with old columns past the table", _lib.HipError)
+def _():
+    import _pam_probe as pp
+    (rc, rG), (cc, cG) = _pairs_inputs()
+    pp.tables(0, rc, rG, cc, cG, 7, 60, 9)
 
 
 @raises("JointCounts too large for the device", InsufficientResourceError)

@@ -5,7 +5,10 @@ float32 certificate's range of q.  Every other GPU test draws from
 enspara_amd.synth (generic chains at nanometre scale); the degenerate spectra of
 tests/_qcp_cases.py reach ek_qcp_probe_kernel alone.  Here the frames go through
 ek_step_kernel<FPL, .>, ek_pass2_kernel, ek_pass16_kernel (certificate, queue,
-dense fallback), the three nearest-center kernels and the ek_pam_pairs* kernels.
+dense fallback), the three nearest-center kernels and the streaming form of a PAM
+sweep.  (The ek_pam_pairs* kernels and the windows in one workgroup need 16384
+frames and K well above 128: the families go through them in
+tests/test_gpu_pam_pairs.py.)
 
 Bars as everywhere: center indices and labels equal, distances equal as float32
 bits to oracle.qcp / oracle.cluster.  No case is skipped: where the oracle raises
@@ -151,10 +154,14 @@ def test_assign_nearest(family, A):
 
 @pytest.mark.parametrize("family,A", CASES)
 def test_one_pam_sweep(family, A):
-    """hybrid(..., n_iters=1) at K = 20 -- its two steps on one store, so that the
-    options can be set: the window's distance kernels on the matrix cores and
-    LDS-staged (process-wide: always said, and left at its default), windows in
-    one workgroup and in three launches per proposal"""
+    """hybrid(..., n_iters=1) at K = 20 -- its two steps on one store.  1000 frames
+    reach the STREAMING form of the sweep only (a pass over all frames per group of
+    proposals, three launches per proposal): ek_pam_prefetch_vectors takes the
+    window's form -- ek_pam_pairs_kernel / ek_pam_pairs16_kernel, ek_pam_active_kernel,
+    the window in one workgroup -- from 16384 frames on, so the two options set
+    below (pam_pairs_mfma is process-wide: always said, and left at its default)
+    select nothing here and the four runs are the same run.  The families go
+    through those kernels in tests/test_gpu_pam_pairs.py::test_structure_families."""
     from enspara_amd.cluster import kcenters as kc
     from enspara_amd.cluster import kmedoids as km
     from oracle import cluster as oc

@@ -33,6 +33,7 @@ SYMBOLS = [
     "ek_spec_apply", "ek_spec_round_end", "ek_spec_progress", "ek_spec_rounds",
     "ek_spec_chain_bytes", "ek_spec_chain_rows", "ek_spec_chain_max",
     "ek_spec_chain_apply", "ek_run_stats", "ek_ti_stats", "ek_view_stats",
+    "ek_last_run_form",
     "ek_view_layout_check",
     "ek_ms_setup", "ek_ms_mailbox", "ek_ms_connect", "ek_ms_begin", "ek_ms_local",
     "ek_ms_global", "ek_ms_end", "ek_ms_run", "ek_ms_state", "ek_ms_diag",
@@ -199,6 +200,7 @@ def load():
     L.ek_ms_run.argtypes = [vp, i32, i32, C.c_double, i32p, i64p, f32p, f32p]
     L.ek_ti_stats.argtypes = [vp, i64p, i64p]
     L.ek_view_stats.argtypes = [vp, i64p]
+    L.ek_last_run_form.argtypes = [vp, i64p]
     L.ek_view_layout_check.argtypes = [vp, f32, i64p]
     L.ek_assign_nearest.argtypes = [vp, f32p, i32]
     f64p = C.POINTER(C.c_double)

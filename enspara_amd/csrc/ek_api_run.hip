@@ -142,7 +142,7 @@ void ek_round_of(ek_ctx *c, int T, double cutoff, EkRound &R)
     // million frames: 10 % of a fit at 125 000; at 10^6 the pass's extra instructions
     // cost what the chain kernel's sweep did, profiles/r06/sweep_ab_*.log)
     R.sweep = (c->pass_sweep == 2 ||
-               (c->pass_sweep == 1 && c->n <= (int64_t)2048 * EK_TILE)) ? 1 : 0;
+               (c->pass_sweep == 1 && ek_sweep_pays(c->n))) ? 1 : 0;
     R.top = c->top;
     R.ctile = c->ctile;
     R.ctrace = c->ctrace;
@@ -153,6 +153,23 @@ void ek_round_of(ek_ctx *c, int T, double cutoff, EkRound &R)
     R.vmask = c->vmask;
     R.cutoff = cutoff;
     R.pick_cap = c->pick_cap > 0 ? c->pick_cap : 4;
+}
+
+// ---- which form the run takes (ek_last_run_form) ------------------------------------------
+// Over the shard's whole store, for the widest form of the run (Tmax candidates; 1: steps
+// of one center alone): a view has frame counts of its own, and the ladder's narrower
+// forms read shorter or equal lists.
+static void ek_note_run_form(ek_ctx *c, int fpl, int nt, bool fused, int Tmax, int sweep,
+                             bool fine_buf)
+{
+    const int nb = (int)((c->n + EK_BLOCK - 1) / EK_BLOCK);
+    const bool fine = fused && Tmax > 1 && fine_buf && ek_fine_fits(nb);
+    c->last_form[0] = fpl;
+    c->last_form[1] = nt ? 1 : 0;
+    c->last_form[2] = sweep ? 1 : 0;
+    c->last_form[3] = fine ? 1 : 0;
+    c->last_form[4] = nb;
+    c->last_form[5] = Tmax > 1 ? (fine ? 4 * (int64_t)nb : nb) : ek_step_blocks(fpl, c->n);
 }
 
 // ---- k-centers rounds on one shard, in the form that pays (ek_run_policy.h) -----------------
@@ -256,7 +273,7 @@ static void ek_run_use_store(EkRun &run, bool the_view)
     }
     run.nb = (int)((R.n + EK_BLOCK - 1) / EK_BLOCK);
     R.sweep = (run.fused && (c->pass_sweep == 2 ||
-                             (c->pass_sweep == 1 && R.n <= (int64_t)2048 * EK_TILE))) ? 1 : 0;
+                             (c->pass_sweep == 1 && ek_sweep_pays(R.n)))) ? 1 : 0;
     // (under a view no center is accepted at or below its guard: the stop rule
     // itself refuses it -- chain walk, plan and step kernel alike)
     R.cutoff = the_view ? std::max(run.dist_cutoff, run.view.guard) : run.dist_cutoff;
@@ -673,6 +690,8 @@ static int ek_run_rounds_in(ek_ctx *c, int Tmax, int32_t first_label,
     R.ti_tab = tri ? c->ti_rtab : nullptr;
     R.ti_stats = tri ? c->ti_stats : nullptr;
     ek_run_use_store(run, false);
+    // (only a round of exactly 16 candidates has the pass sweep: ek_round_chain_kernel)
+    ek_note_run_form(c, run.fpl, run.nt, fused, Tmax, R.sweep && Tmax == 16, R.fm != nullptr);
     EK_HIP(hipEventRecord(c->ev0, c->stream));
     while (run.cr.n_done < goal) {
         const int32_t left = goal - run.cr.n_done;
@@ -776,6 +795,9 @@ extern "C" int ek_kcenters_run(ek_ctx *c, int32_t first_label, int32_t max_new,
     // With no distance cut-off the trip count is known: enqueue everything.
     // With a cut-off, enqueue in batches and look at the stop flag in between
     // (steps enqueued past the stopping point are no-ops on the device).
+    ek_note_run_form(c, ek_pick_fpl(c), ek_pick_nt(c), false, 1, 0, false);
+    // (this loop has no view: ek_view_stats must not go on telling of an earlier run's)
+    c->view_stats[0] = c->view_stats[1] = c->view_stats[2] = c->view_stats[3] = 0;
     const bool open_loop = !(dist_cutoff > 0.0);
     const int32_t batch = open_loop ? max_new : 16;
     int32_t issued = 0;
@@ -898,6 +920,15 @@ extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
     out[1] = (int64_t)got[0];
     out[2] = (int64_t)got[1];
     out[3] = (int64_t)got[2];
+    return EK_OK;
+}
+
+extern "C" int ek_last_run_form(ek_ctx *c, int64_t *out)
+{
+    if (!c || !out)
+        return ek_fail(EK_EARG, "ek_last_run_form: NULL argument");
+    for (int k = 0; k < 6; ++k)
+        out[k] = c->last_form[k];
     return EK_OK;
 }
 

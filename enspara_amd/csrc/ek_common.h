@@ -66,6 +66,22 @@ typedef float ek_v2f __attribute__((ext_vector_type(2)));
 // the widest form of the one-launch-per-step kernels (ek_chain.hip, the ek_spec_*
 // protocol, option key 10 = 0): their per-thread arrays are sized for this
 #define EK_LEGACY_CANDS 16
+// ---- where a round changes form with the number of frames: one source each ---------
+// (kernel, launcher and ek_last_run_form all ask here; tests/test_gpu_frame_counts.py
+// sits on both sides of each)
+#define EK_RED_THREADS 1024     // the single-workgroup reductions over the block maxima
+// rounds of 16: the pass takes the per-prefix maxima itself (EK_OPT_PASS_SWEEP = 1) on
+// stores of up to 2048 tiles; above, the chain kernel's sweep (ek_api_run.hip)
+__host__ __device__ inline bool ek_sweep_pays(int64_t n)
+{
+    return n <= (int64_t)2048 * EK_TILE;
+}
+// the candidate pick reads the maxima per 64 frames (four per block of 256) while they
+// fit the eight entries per thread of ek_pick_top_body; above, the maxima per 256
+__host__ __device__ inline bool ek_fine_fits(int nb)
+{
+    return 4 * nb <= 8 * EK_RED_THREADS;
+}
 // PAM: proposals per prefetch pass / columns per workgroup of the pairs kernel
 #define EK_PAM_GROUP 8
 // plan of one multi-candidate round (ek_spec.hip); written only by the

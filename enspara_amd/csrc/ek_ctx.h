@@ -284,6 +284,7 @@ struct ek_ctx {
     int adapt = 1;               // choose the candidates per pass from measured rates
     int64_t st_rounds[EK_N_FORMS] = {0, 0, 0, 0, 0};    // rounds run as 1 / 4 / 8 / 16 / 32 candidates (last run)
     int64_t st_centers[EK_N_FORMS] = {0, 0, 0, 0, 0};   // centers they accepted
+    int64_t last_form[6] = {0, 0, 0, 0, 0, 0};          // ek_last_run_form (last ek_kcenters_run)
     hipEvent_t evb0 = nullptr, evb1 = nullptr;   // per-batch timing
 
     // active view (ek_view.hip, ek_run_rounds): a second frame store of the frames no

@@ -65,7 +65,7 @@ ek_round_chain_kernel(EkRound r, int bootstrap)
     // fewer rounds at 125 000 --; at 10^6 they changed 358 rounds to 355 and cost the
     // pick 10 us per round, two batches of loads instead of one: there it reads the
     // maxima per 256)
-    const bool fine_ok = r.fm != nullptr && 4 * nb <= 8 * EK_RED_THREADS;
+    const bool fine_ok = r.fm != nullptr && ek_fine_fits(nb);
 #ifdef EK_ROUND_STAMPS
     unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif

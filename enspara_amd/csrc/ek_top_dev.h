@@ -5,7 +5,7 @@
 #include "ek_common.h"
 #include "ek_reduce.h"
 
-#define EK_RED_THREADS 1024
+// (EK_RED_THREADS: ek_common.h)
 
 // (max, first index) over blockmax[0..nb) skipping entries whose block is
 // marked in `skip` (LDS bitmap, may be null) -> all threads get the result
@@ -187,6 +187,12 @@ __device__ __forceinline__ void ek_pick_top_body(const EkBlockMax *blockmax, int
         // LARGEST of its strided share -- the pool below holds ~128 entries of the
         // whole list, and more than eight of them in one thread's share of sixteen
         // do not happen; if they did it would cost a guess, never a result.
+        // (What IS a result is entry 0, taken as a center unchecked, and it rests on this
+        // tail: a slot is replaced only by a strictly larger value and only when it is the
+        // smallest, so the first entry carrying the maximum of a thread's share is never
+        // dropped, and the shard's first-index arg-max is that entry of its thread.  A
+        // build without the tail returns other centers as soon as the maximum lies behind
+        // entry 8192: tests/test_gpu_frame_counts.py, the "tail" data at 2 098 177 frames.)
         // entries per thread actually in use (uniform: the loops skip the rest)
         const int per = nb >= PICK_PER * EK_RED_THREADS
                             ? PICK_PER : (nb + EK_RED_THREADS - 1) / EK_RED_THREADS;

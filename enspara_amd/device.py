@@ -579,6 +579,18 @@ class FrameStore:
         return {"views": int(s[0]), "streamed": int(s[1]), "left_out": int(s[2]),
                 "guard_exits": int(s[3])}
 
+    def last_run_form(self):
+        """Which form the last kcenters_run took where the kernels change form with the
+        number of frames (ek_last_run_form; whole store, widest form of the run):
+        -> {"frames_per_lane", "nontemporal", "sweep_in_pass", "fine_pick",
+        "coarse_entries": blocks of 256 frames, "pick_entries": entries of the longest
+        list the candidate pick reads}"""
+        s = np.zeros(6, dtype=np.int64)
+        _lib.check(self.lib.ek_last_run_form(self._h, _lib.i64p(s)))
+        return {"frames_per_lane": int(s[0]), "nontemporal": int(s[1]),
+                "sweep_in_pass": int(s[2]), "fine_pick": int(s[3]),
+                "coarse_entries": int(s[4]), "pick_entries": int(s[5])}
+
     def view_layout_check(self, theta):
         """TEST entry: the view of the frames above ``theta`` built as a rebuild builds
         it, against the earlier path's layouts -> (frames in the view, differing words

@@ -286,6 +286,23 @@ int ek_ti_stats(ek_ctx *ctx, int64_t *tiles, int64_t *skipped);
  * [1] frames x rounds streamed, [2] frames x rounds left out, [3] views ended by
  * their guard (the maximum fell to it before the run stopped). */
 int ek_view_stats(ek_ctx *ctx, int64_t *stats);
+/* Which form the last ek_kcenters_run took where the kernels change form with the number
+ * of frames.  Read-only: no launch, no allocation.  out[6], all for the shard's whole
+ * store (an active view has frame counts of its own) and the widest form of the run:
+ *   [0] frames per lane of the one-center step kernel (1, 2, 4; automatic from 524 161
+ *       and 1 048 321 frames)
+ *   [1] non-temporal frame loads, 0 / 1
+ *   [2] rounds of 16 take the per-prefix maxima in the pass, 0 / 1 (EK_OPT_PASS_SWEEP;
+ *       automatic up to 524 288 frames; always 0 unless the widest form is 16 in fused
+ *       rounds)
+ *   [3] the candidate pick reads maxima per 64 frames, 0 / 1 (EK_OPT_FINE_PICK, fused
+ *       rounds, up to 524 288 frames)
+ *   [4] entries of the coarse list: blocks of 256 frames
+ *   [5] entries of the longest list the pick reads: 4 x [4] with [3] on, [4] in other
+ *       rounds, the step kernel's workgroups (256 x [0] frames each) where the run takes
+ *       one center per pass only
+ * All zero before the first run.  No reference counterpart. */
+int ek_last_run_form(ek_ctx *ctx, int64_t *out);
 /* TEST entry.  Selects the frames whose distance is above theta, builds their view as a
  * rebuild does (into buffers filled with 0xFF bytes; the frame-minor tiles on demand
  * from the quad copy where the context has one) and, in scratch of its own, the same

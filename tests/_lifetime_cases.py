@@ -166,6 +166,14 @@ def _(st):
     return _run(st, 16)
 
 
+# (ek_last_run_form reads six numbers the run left in the context: no allocation, no
+# launch -- rounds of 8 without a view, so that none of the run's own may be survived)
+@handle("FrameStore.kcenters_run + last_run_form, 8 candidates, no active view", _open_frames)
+def _(st):
+    st.set_option("active_view", 0)
+    return _run(st, 8), st.last_run_form()
+
+
 @handle("FrameStore.assign_nearest", _open_frames)
 def _(st):
     st.assign_nearest(_frames()[[0, 17, 99, 256, 299]])

@@ -67,6 +67,8 @@ SYMBOLS = [
     "ek_pockets_open", "ek_pockets_run", "ek_pockets_counts", "ek_pockets_fetch",
     "ek_pockets_last_timing", "ek_pockets_close", "ek_pockets_touches", "ek_pockets_ranks",
     "ek_pockets_labels",
+    "ek_dyes_open", "ek_dyes_run", "ek_dyes_counts", "ek_dyes_fetch", "ek_dyes_last_timing",
+    "ek_dyes_close", "ek_dyes_touches", "ek_dyes_pair_hist",
     "ek_rotamer_states", "ek_dihedral_angles", "ek_dihedral_rotamers",
     "ek_krylov_create", "ek_krylov_destroy", "ek_krylov_set_vector",
     "ek_krylov_get_vector", "ek_krylov_step", "ek_krylov_rotate",
@@ -310,6 +312,15 @@ def load():
     L.ek_pockets_touches.argtypes = [C.c_int, f32p, i32, f64p, C.c_double, f32p, i32p, u8p]
     L.ek_pockets_ranks.argtypes = [C.c_int, u8p, i32p, u8p]
     L.ek_pockets_labels.argtypes = [C.c_int, u8p, i32p, i32p]
+    L.ek_dyes_open.argtypes = [C.c_int, i32, f64p, i32, f32p, i32, f32p, C.c_double,
+                               C.POINTER(vp)]
+    L.ek_dyes_run.argtypes = [vp, f32p, i64, f32p, i64]
+    L.ek_dyes_counts.argtypes = [vp, i64, i32p, i32p]
+    L.ek_dyes_fetch.argtypes = [vp, i64p]
+    L.ek_dyes_last_timing.argtypes = [vp, f64p]
+    L.ek_dyes_close.argtypes = [vp]
+    L.ek_dyes_touches.argtypes = [C.c_int, f32p, i32, f64p, f32p, i32, u8p]
+    L.ek_dyes_pair_hist.argtypes = [C.c_int, f32p, i32, f32p, i32, C.c_double, i32p, i64p]
     L.ek_rotamer_states.argtypes = [C.c_int, f32p, i64, i32, u8p, i32, i32p, f64p, f32p,
                                     C.c_double, u8p, f64p]
     L.ek_dihedral_angles.argtypes = [C.c_int, f32p, i64, i32, i32p, i32, f32p, f64p]

@@ -781,6 +781,66 @@ int ek_pockets_ranks(int device, const uint8_t *touches, const int32_t *dims,
 int ek_pockets_labels(int device, const uint8_t *mask, const int32_t *dims,
                       int32_t *labels_out);
 
+/* ---- smFRET dye labelling ---------------------------------------------------------------
+ * Replaces dye_distance_distribution of enspara/geometry/dyes_from_expt_dist.py and what it
+ * calls (csrc/ek_dyes.hip; the contract is DESIGN.md 4l).  All arrays are host memory.
+ * A handle holds, on the device, cutoff [atoms] float64 = radius + probe in nm (> 0 and
+ * finite), the two point clouds dye1 [n1][3], dye2 [n2][3] float32 in nm (finite, 1 <= n <=
+ * 2^20) and bin_width (> 0, finite).
+ * ek_dyes_run: xyz [frames][atoms][3] float32 in nm, finite; Mt [frames][2][12] float32 =
+ * per frame and labelled residue the rotation M (row-major, 9) and the translation t (3),
+ * finite: the caller makes them on the host.  Placement 0 = dye1 on residue 0, 1 = dye1 on
+ * residue 1, 2 = dye2 on residue 0, 3 = dye2 on residue 1; pair 0 = placements (0, 3), pair
+ * 1 = placements (1, 2).
+ * Alignment, float32, nothing fused: p_j = ((x*M[0][j] + y*M[1][j]) + z*M[2][j]) + t[j].
+ * Touch test, float64: a point is kept iff for every atom sqrt((dx*dx + dy*dy) + dz*dz) >
+ * cutoff, d = double(atom) - double(point), the square root correctly rounded.  The kernel
+ * compares the squared distance with the smallest double whose correctly rounded square
+ * root exceeds the cutoff (made on the host): the same set, no square root.  Kept points
+ * keep their order.
+ * Histogram of all distances between two clouds (n1 points, n2 points), float64 distances
+ * by the same formula: if n1 * n2 <= 5e7 the pairs are one chunk; otherwise the larger
+ * cloud (the second on a tie) is cut into chunks of 2048 consecutive points.  Per chunk c:
+ * dmax_c = its largest distance, nbins_c = int(dmax_c / bin_width) + 2, step_c = (nbins_c *
+ * bin_width) / nbins_c, edge k = double(k) * step_c, and a distance counts in bin k iff
+ * edge_k <= d < edge_{k+1}.  The chunks' counts are added bin by bin (int64); nbins = the
+ * largest nbins_c.  The kernels take no square root: dmax_c / bin_width >= m and d >= edge_k
+ * are decided on the squared distance against thresholds that are the exact images of those
+ * conditions under a correctly rounded square root and division (host tables).  Counts are
+ * taken with integer atomics only: every run gives the same bits.
+ * Bound: nbins_c <= 4096.  The diagonal of the box that holds both clouds (times 1 + 2^-16)
+ * must be below 4093 bin widths; in a run the box holds, per residue and axis j, t_j +- (rho
+ * |column j of M| + (|t_j| + rho |column j of M|) 2^-20) (1 + 2^-16), rho the largest norm
+ * of a point of either cloud.  Coordinates are at most 2^20 nm in magnitude and bin_width
+ * lies in [2^-40, 2^40] (EK_EARG).
+ * chunk_frames > 0: frames of one upload (at most 4096; EK_ENOMEM if they do not fit); 0:
+ * what fits half of the free device memory.  Per chunk of frames: one upload of xyz and Mt,
+ * the kernels, one download of kept counts, nbins and counts.
+ * ek_dyes_counts: kept_out [frames][4] = the kept points of every placement, nbins_out
+ * [frames][2] = nbins of every pair (0 where a placement of the pair kept nothing) of the
+ * last run (frames must be that run's).  ek_dyes_fetch: counts_out [sum of nbins] int64,
+ * frame after frame, pair 0 then pair 1.  ek_dyes_last_timing: ms_out[4] = the last run's
+ * uploads, touch and compaction kernels, histogram kernels, downloads, summed over its
+ * chunks, between HIP events.
+ * Each stage alone: ek_dyes_touches: xyz [atoms][3], cutoff [atoms], coords [n][3] float32
+ * (as they are: no alignment) -> keep_out [n] bytes 0 / 1.  ek_dyes_pair_hist: coords1
+ * [n1][3], coords2 [n2][3] float32 -> *nbins_out and counts_out [4096] int64, zero from
+ * nbins on. */
+typedef struct ek_dyes ek_dyes;
+int ek_dyes_open(int device, int32_t atoms, const double *cutoff, int32_t n1,
+                 const float *dye1, int32_t n2, const float *dye2, double bin_width,
+                 ek_dyes **out);
+int ek_dyes_run(ek_dyes *h, const float *xyz, int64_t frames, const float *Mt,
+                int64_t chunk_frames);
+int ek_dyes_counts(ek_dyes *h, int64_t frames, int32_t *kept_out, int32_t *nbins_out);
+int ek_dyes_fetch(ek_dyes *h, int64_t *counts_out);
+int ek_dyes_last_timing(ek_dyes *h, double *ms_out);
+int ek_dyes_close(ek_dyes *h);
+int ek_dyes_touches(int device, const float *xyz, int32_t atoms, const double *cutoff,
+                    const float *coords, int32_t n, uint8_t *keep_out);
+int ek_dyes_pair_hist(int device, const float *coords1, int32_t n1, const float *coords2,
+                      int32_t n2, double bin_width, int32_t *nbins_out, int64_t *counts_out);
+
 /* ---- joint probabilities and mutual information of weighted frames --------------------
  * Replaces the arithmetic of weighted_mi (enspara/info_theory/mutual_info.py:78-178;
  * csrc/ek_wmi.hip).  codes [frames][F] state codes as bytes (the caller validates them:

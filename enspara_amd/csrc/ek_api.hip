@@ -898,9 +898,9 @@ extern "C" int ek_history_reset(ek_ctx *c)
 // frames a window's proposals can touch, +inf for the rest) no longer holds
 void ek_pam_forget(ek_ctx *c)
 {
-    c->pf_count = 0;
-    c->tab_n = 0;
-    c->sp_ready = false;
+    c->pf.invalidate();
+    c->tab.invalidate();
+    c->sp.invalidate();
 }
 
 extern "C" int ek_state_reset(ek_ctx *c)

@@ -94,15 +94,10 @@ static int ek_pam_alloc(ek_ctx *c, int32_t K)
             EK_HIP(ek_pinned_malloc((void **)&c->pam_win_host, sizeof(EkPamWin),
                              hipHostMallocCoherent | hipHostMallocMapped));
     }
-    c->pam_restore = -1;
-    c->pf_backoff = 0;
-    c->sp_ready = false;
-    c->sp_backoff = 0;
-    c->sp_backoff_next = 8;
-    c->bat_cid0 = -1;
-    c->bat_count = 0;
-    c->pf_count = 0;
-    c->pf_external = false;
+    c->tab.restore = -1;
+    c->sp.begin();
+    c->cnt.invalidate_batch();
+    c->pf.begin();
     if (K > c->med_cap) {
         EK_HIP(ek_wait(c));
         (void)ek_dev_free(c->med_aos);
@@ -127,8 +122,8 @@ static int ek_pam_alloc(ek_ctx *c, int32_t K)
     }
     c->med_K = K;
     c->pam_cid = -1;
-    c->cnt_cid = -1;
-    c->tab_n = 0;
+    c->cnt.invalidate_one();
+    c->tab.invalidate();
     return EK_OK;
 }
 
@@ -235,8 +230,7 @@ extern "C" int ek_pam_count_members(ek_ctx *c, int32_t cid, int64_t *count)
     EK_HIP(hipMemcpyAsync(count, c->sel, sizeof(int64_t), hipMemcpyDeviceToHost,
                           c->stream));
     EK_HIP(ek_wait(c));
-    c->cnt_cid = cid;
-    c->cnt_m = *count;
+    c->cnt.one(cid, *count);
     return EK_OK;
 }
 
@@ -279,18 +273,12 @@ static int ek_pam_tail(ek_ctx *c, int32_t cid, const float *newd,
 {
     const int K = c->med_K;
     const int fuse = decide != nullptr;
-    c->sp_ready = false;        // c->amb is the ambiguous members' list from here on
-    // only when dist[f] is known to be the distance to medoid assign[f] (a state
-    // this library produced; not one uploaded by the caller) may the search skip
-    // medoids out of the members' reach
-    // (and not for 1- or 2-atom "structures": collinear points make the largest
-    // root of the QCP quartic a double root, the computed distances are then too
-    // erratic to be treated as a metric)
-    const bool prune = c->prune && c->state_exact && c->A >= 3;
+    c->sp.invalidate();         // c->amb is the ambiguous members' list from here on
+    const bool prune = ek_pam_prune_ok(c->prune, c->state_exact, c->A);
     // inside a window whose distance tables are in place the classification's
     // last workgroup lists the medoids within reach itself
-    const bool tabs = fuse && prune && c->tab_lo == cid - decide->slot &&
-                      decide->slot < c->tab_n;
+    const bool tabs = fuse && prune && c->tab.lo == cid - decide->slot &&
+                      decide->slot < c->tab.n;
     if (fuse) {
         const size_t tb = (size_t)EK_PAM_WIN * (c->med_cap + 1);
         EkPamClsWin w;
@@ -359,10 +347,10 @@ static int ek_pam_amb_room(ek_ctx *c, int64_t max_amb)
 // the prefetched distance vector of a local frame, or nullptr
 static const float *ek_pam_prefetched(ek_ctx *c, int64_t frame_index)
 {
-    if (frame_index < 0 || c->pf_external)
+    if (frame_index < 0 || c->pf.external)
         return nullptr;
-    for (int32_t j = 0; j < c->pf_count; ++j)
-        if (c->pf_frames[j] == frame_index)
+    for (int32_t j = 0; j < c->pf.count; ++j)
+        if (c->pf.frames[j] == frame_index)
             return c->pam_vecs + (size_t)j * c->n_pad;
     return nullptr;
 }
@@ -382,9 +370,9 @@ static int ek_pam_propose_impl(ek_ctx *c, int32_t cid, int64_t frame_index,
         return rc;
     const float *newd = ek_pam_prefetched(c, frame_index);
     if (newd)
-        ++c->pf_hits;
+        ++c->pf.hits;
     else
-        ++c->pf_misses;
+        ++c->pf.misses;
     const int64_t *idx_dev = c->sel + 1;    // read only when frame_index < 0
     if (!newd) {
         // distances of every frame to the proposed medoid (kmedoids.py:637)
@@ -399,11 +387,11 @@ static int ek_pam_propose_impl(ek_ctx *c, int32_t cid, int64_t frame_index,
         newd = c->scratch;
     }
     // trial medoid table (undoing a rejected proposal's row first), counters
-    c->tab_n = 0;
+    c->tab.invalidate();
     ek_launch_pam_trial(c->tiles, c->G, c->A, c->med_aos, c->med_G, K, cid,
-                        c->pam_restore, frame_index, idx_dev, nullptr, nullptr,
+                        c->tab.restore, frame_index, idx_dev, nullptr, nullptr,
                         c->amb_count, c->moved, c->stream);
-    c->pam_restore = -1;
+    c->tab.restore = -1;
     rc = ek_pam_tail(c, cid, newd, max_amb, win_lo, moved_mask ? win_count : 0,
                      c->pam_out_dev);
     if (rc)
@@ -463,14 +451,14 @@ extern "C" int ek_pam_propose(ek_ctx *c, int32_t cid, int64_t frame_index,
                        (long long)frame_index);
     EK_HIP(hipSetDevice(c->device));
     int64_t m = 0;
-    if (c->cnt_cid == cid) {
-        m = c->cnt_m;
+    if (c->cnt.cid == cid) {
+        m = c->cnt.m;
     } else {
         rc = ek_pam_count_members(c, cid, &m);
         if (rc)
             return rc;
     }
-    c->cnt_cid = -1;
+    c->cnt.invalidate_one();
     return ek_pam_propose_impl(c, cid, frame_index, m, nullptr, old_cost,
                                new_cost, n_ambiguous);
 }
@@ -482,18 +470,18 @@ extern "C" int ek_pam_propose_member(ek_ctx *c, int32_t cid, int64_t j,
     int rc = ek_pam_precheck(c, cid, "ek_pam_propose_member");
     if (rc)
         return rc;
-    if (c->cnt_cid != cid)
+    if (c->cnt.cid != cid)
         return ek_fail(EK_ESTATE, "ek_pam_propose_member: call "
                                   "ek_pam_count_members(%d) first", cid);
-    if (j < 0 || j >= c->cnt_m)
+    if (j < 0 || j >= c->cnt.m)
         return ek_fail(EK_EARG, "ek_pam_propose_member: member %lld of %lld",
-                       (long long)j, (long long)c->cnt_m);
+                       (long long)j, (long long)c->cnt.m);
     EK_HIP(hipSetDevice(c->device));
     ek_launch_select_member(c->assign, c->n, cid, c->scan, j, c->sel + 1,
                             c->stream);
     EK_CHECK_LAUNCH();
-    const int64_t m = c->cnt_m;
-    c->cnt_cid = -1;
+    const int64_t m = c->cnt.m;
+    c->cnt.invalidate_one();
     return ek_pam_propose_impl(c, cid, -1, m, frame_index, old_cost, new_cost,
                                n_ambiguous);
 }
@@ -510,10 +498,10 @@ extern "C" int ek_pam_commit(ek_ctx *c, int accept)
         std::swap(c->assign, c->nassign);
     } else {
         // the trial row is put back by the next proposal's first kernel
-        c->pam_restore = c->pam_cid;
+        c->tab.restore = c->pam_cid;
     }
     c->pam_cid = -1;
-    c->cnt_cid = -1;
+    c->cnt.invalidate_one();
     return EK_OK;
 }
 
@@ -540,16 +528,13 @@ extern "C" int ek_pam_count_members_batch(ek_ctx *c, int32_t cid0, int32_t count
                                 "outside [0,%d) or more than %d", cid0, count,
                        c->med_K, EK_PAM_WIN);
     EK_HIP(hipSetDevice(c->device));
-    const size_t nb = ((size_t)std::max<int64_t>(c->n, 1) + EK_BLOCK - 1) / EK_BLOCK;
-    (void)nb;
     ek_launch_count_members_multi(c->assign, c->n, cid0, count, c->bat_blockcnt,
                                   c->bat_scan, c->bat_sel, c->stream);
     EK_CHECK_LAUNCH();
     EK_HIP(hipMemcpyAsync(counts, c->bat_sel, (size_t)count * sizeof(int64_t),
                           hipMemcpyDeviceToHost, c->stream));
     EK_HIP(ek_wait(c));
-    c->bat_cid0 = cid0;
-    c->bat_count = count;
+    c->cnt.batch(cid0, count);
     return EK_OK;
 }
 
@@ -558,13 +543,11 @@ extern "C" int ek_pam_select_members_batch(ek_ctx *c, int32_t cid0, int32_t coun
 {
     if (!c || !js || !frames)
         return ek_fail(EK_EARG, "ek_pam_select_members_batch: NULL argument");
-    if (c->bat_cid0 != cid0 || count < 1 || count > c->bat_count)
+    if (!c->cnt.batch_covers(cid0, count))
         return ek_fail(EK_ESTATE, "ek_pam_select_members_batch: call "
                                   "ek_pam_count_members_batch(%d, >=%d) first",
                        cid0, count);
     EK_HIP(hipSetDevice(c->device));
-    const size_t nb = ((size_t)std::max<int64_t>(c->n, 1) + EK_BLOCK - 1) / EK_BLOCK;
-    (void)nb;
     // (a negative rank: that member lives on another shard)
     EK_HIP(hipMemcpyAsync(c->bat_sel + 2 * EK_PAM_WIN, js,
                           (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice,
@@ -577,13 +560,29 @@ extern "C" int ek_pam_select_members_batch(ek_ctx *c, int32_t cid0, int32_t coun
                           (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost,
                           c->stream));
     EK_HIP(ek_wait(c));
-    // the scans describe the state at count time only
-    c->bat_cid0 = -1;
-    c->bat_count = 0;
+    c->cnt.invalidate_batch();
     for (int32_t j = 0; j < count; ++j)
         if (frames[j] < 0 && js[j] >= 0)
             return ek_fail(EK_EARG, "ek_pam_select_members_batch: cluster %d has "
                                     "no member %lld", cid0 + j, (long long)js[j]);
+    return EK_OK;
+}
+
+// A pinned host buffer of `count` elements the device can address, made when first
+// asked for, and (want) its device view: nullptr where the mapping fails -- the caller
+// copies instead.
+template <class T>
+static int ek_mapped(T **host, size_t count, bool want, T **dev_view)
+{
+    *dev_view = nullptr;
+    if (!*host)
+        EK_HIP(ek_pinned_malloc((void **)host, count * sizeof(T),
+                                hipHostMallocCoherent | hipHostMallocMapped));
+    void *dp = nullptr;
+    if (want && hipHostGetDevicePointer(&dp, *host, 0) == hipSuccess)
+        *dev_view = (T *)dp;
+    else if (want)
+        (void)hipGetLastError();
     return EK_OK;
 }
 
@@ -605,106 +604,98 @@ static int ek_pam_vecs_alloc(ek_ctx *c)
     return EK_OK;
 }
 
-// The distance vectors of the `count` records in c->pam_recs.  When the state is
-// exact (every frame's distance is the distance to the medoid its label names)
-// and the window of clusters being worked through is known, only the frames a
-// proposal can touch get exact distances (ek_pam.hip, "proposal prefetch
-// restricted ..."): the others get +inf.
-// local: the proposals are frames of this shard, proposal j for cluster
-// win_lo + j when win_count == count (the layout ek_pam_window_run expects)
-// prepared: ek_launch_pam_setup made the records (plan, candidate tile and the
-// cleared active-frame counter come with them)
-static int ek_pam_prefetch_vectors(ek_ctx *c, int count, int32_t win_lo,
-                                   int32_t win_count, bool local,
-                                   bool prepared = false, bool *waited = nullptr)
+// the three blocks of c->dtab: T, O at + tb, dmin at + 2 tb
+static size_t ek_pam_tab_block(const ek_ctx *c) { return (size_t)EK_PAM_WIN * (c->med_cap + 1); }
+
+// The window's tables and, from them, the list of the frames its proposals can touch
+// (c->act_list), its length read back: one wait.  Tables made as bounds that list too
+// many are made again exactly (the policy's retry).
+static int ek_pam_list_within_reach(ek_ctx *c, int count, int32_t win_lo, int32_t win_count,
+                                    bool slots, bool prepared, bool bounds, int64_t *n_act)
 {
-    if (waited)
-        *waited = false;
-    c->tab_n = 0;
-    c->sp_ready = false;
     const int K = c->med_K;
-    if (c->pf_backoff > 0)
-        --c->pf_backoff;
-    else if (c->prune && c->state_exact && c->A >= 3 && win_count > 0 &&
-             c->n >= 16384) {
-        if (!c->act_n_host)
-            EK_HIP(ek_pinned_malloc((void **)&c->act_n_host, sizeof(unsigned int),
-                                 hipHostMallocDefault));
+    const size_t tb = ek_pam_tab_block(c);
+    const int groups = (count + EK_PAM_GROUP - 1) / EK_PAM_GROUP;
+    for (int attempt = 0;; ++attempt) {
         // O (old medoids of the window's clusters) only where the window's slots
         // and the proposals coincide: ek_pam_window_run's pruning reads it
-        const bool slots = local && win_count == count;
-        const size_t tb = (size_t)EK_PAM_WIN * (c->med_cap + 1);
-        const int groups = (count + EK_PAM_GROUP - 1) / EK_PAM_GROUP;
-        // (proposals drawn among their clusters' members, ek_pam_sweep: the
-        // proposal-to-medoid table only as the lower bounds the old medoids'
-        // table gives, half the pairs -- ek_pam_pairs_kernel<0>.  Where the bounds
-        // are too loose -- few atoms, clusters as wide as they are apart: more than
-        // a quarter of the frames "within reach" -- the window's tables are made
-        // again exactly, and the next windows' right away)
-        bool bounds = slots && prepared && c->pf_members && c->pam_bounds &&
-                      c->pam_bounds_off == 0;
-        if (c->pam_bounds_off > 0)
-            --c->pam_bounds_off;
-        if (!c->act_list)
-            EK_HIP(ek_dev_malloc((void **)&c->act_list,
-                             (size_t)std::max<int64_t>(c->n, 1) * sizeof(uint32_t)));
-        // the vectors go back to +inf: the entries the window before wrote, if
-        // that is all there is (before the list is overwritten)
-        const bool sparse_reset = c->vecs_rows >= 0 && c->vecs_cols >= count;
-        if (sparse_reset)
-            ek_launch_pam_vecs_reset(c->act_list, c->vecs_rows, c->vecs_cols, c->n_pad,
-                                     c->pam_vecs, c->stream);
-        c->vecs_rows = -1;
-        for (int attempt = 0;; ++attempt) {
-            ek_launch_pam_tables(c->med_aos, c->med_G, c->A, K, c->pam_restore,
-                                 c->pam_recs, count, win_lo, slots ? count : 0, c->dtab,
-                                 c->dtab + tb, c->dtab + 2 * tb, c->stream,
-                                 bounds ? c->pam_dprop : nullptr);
-            c->tab_lo = win_lo;
-            c->tab_n = slots ? count : 0;
-            if (attempt > 0)    // (the counter the set-up kernel cleared has been used)
-                EK_HIP(hipMemsetAsync(c->amb_count + 3, 0, sizeof(unsigned int), c->stream));
-            ek_launch_pam_active(c->dist, c->assign, c->n, c->dtab + 2 * tb, groups, K,
-                                 win_lo, win_count, c->act_list, c->amb_count + 3,
-                                 c->stream, prepared || attempt > 0);
-            EK_CHECK_LAUNCH();
-            EK_HIP(hipMemcpyAsync(c->act_n_host, c->amb_count + 3, sizeof(unsigned int),
-                                  hipMemcpyDeviceToHost, c->stream));
-            EK_HIP(ek_wait(c));
-            if (waited)
-                *waited = true;
-            if (!bounds || (int64_t)*c->act_n_host * 4 <= c->n)
-                break;
-            bounds = false;
-            c->pam_bounds_off = 32;
-        }
-        const int64_t n_act = *c->act_n_host;
-        if (n_act * 4 <= c->n) {
-            // a short list: straight from the frame-major copy, 64 frames x the
-            // proposals per workgroup, results scattered into the full vectors
-            // (a quarter of the frames costs about what the passes over all of
-            // them do)
-            if (!sparse_reset)
-                EK_HIP(hipMemsetD32Async((hipDeviceptr_t)c->pam_vecs, 0x7f800000,
-                                         (size_t)count * c->n_pad, c->stream));
-            ek_launch_pam_list_dist(c->aos, c->G, c->A, c->act_list, n_act, c->pam_recs,
-                                    count, c->pam_vecs, c->n_pad, c->stream);
-            EK_CHECK_LAUNCH();
-            c->vecs_rows = n_act;
-            c->vecs_cols = sparse_reset ? c->vecs_cols : count;
-            ++c->pf_sparse;
-            // the list stays in c->amb until something else uses it: a window run
-            // right away may work from it (ek_pam_sparse.hip)
-            c->sp_ready = slots && n_act <= EK_SP_CAP;
-            c->sp_nact = n_act;
+        ek_launch_pam_tables(c->med_aos, c->med_G, c->A, K, c->tab.restore,
+                             c->pam_recs, count, win_lo, slots ? count : 0, c->dtab,
+                             c->dtab + tb, c->dtab + 2 * tb, c->stream,
+                             bounds ? c->pam_dprop : nullptr);
+        c->tab.made(win_lo, slots ? count : 0);
+        if (attempt > 0)    // (the counter the set-up kernel cleared has been used)
+            EK_HIP(hipMemsetAsync(c->amb_count + 3, 0, sizeof(unsigned int), c->stream));
+        ek_launch_pam_active(c->dist, c->assign, c->n, c->dtab + 2 * tb, groups, K,
+                             win_lo, win_count, c->act_list, c->amb_count + 3,
+                             c->stream, prepared || attempt > 0);
+        EK_CHECK_LAUNCH();
+        EK_HIP(hipMemcpyAsync(c->act_n_host, c->amb_count + 3, sizeof(unsigned int),
+                              hipMemcpyDeviceToHost, c->stream));
+        EK_HIP(ek_wait(c));
+        *n_act = *c->act_n_host;
+        if (!c->pf.form.retry_exact(bounds, *n_act, c->n))
             return EK_OK;
-        }
-        // too many frames within reach (large clusters): the test cost a table,
-        // a scan and a read-back for nothing -- leave it out for a while
-        c->pf_backoff = 15;
+        bounds = false;
     }
-    // a pass over all frames per group of EK_PAM_GROUP proposals
-    c->vecs_rows = -1;          // (whole vectors are written)
+}
+
+// The restricted form: exact distances at the listed frames only, +inf elsewhere
+// (ek_pam.hip, "proposal prefetch restricted ...").  *done = false: the list came out
+// too long, nothing was written -- the pass over all frames follows.
+static int ek_pam_prefetch_restricted(ek_ctx *c, int count, int32_t win_lo, int32_t win_count,
+                                      bool local, bool prepared, bool *done)
+{
+    *done = false;
+    if (!c->act_n_host)
+        EK_HIP(ek_pinned_malloc((void **)&c->act_n_host, sizeof(unsigned int),
+                             hipHostMallocDefault));
+    const bool slots = local && win_count == count;
+    // (proposals drawn among their clusters' members, ek_pam_sweep: the
+    // proposal-to-medoid table only as the lower bounds the old medoids'
+    // table gives, half the pairs -- ek_pam_pairs_kernel<0>)
+    const bool bounds =
+        c->pf.form.use_bounds(slots && prepared && c->pf.members && c->pam_bounds);
+    if (!c->act_list)
+        EK_HIP(ek_dev_malloc((void **)&c->act_list,
+                         (size_t)std::max<int64_t>(c->n, 1) * sizeof(uint32_t)));
+    // the vectors go back to +inf: the entries the window before wrote, if
+    // that is all there is (before the list is overwritten)
+    const bool sparse_reset = c->pf.vecs.sparse_reset(count);
+    if (sparse_reset)
+        ek_launch_pam_vecs_reset(c->act_list, c->pf.vecs.rows, c->pf.vecs.cols, c->n_pad,
+                                 c->pam_vecs, c->stream);
+    c->pf.vecs.whole();
+    int64_t n_act = 0;
+    int rc = ek_pam_list_within_reach(c, count, win_lo, win_count, slots, prepared, bounds, &n_act);
+    if (rc)
+        return rc;
+    if (!ek_pf_short(n_act, c->n)) {
+        c->pf.form.too_many();
+        return EK_OK;
+    }
+    // straight from the frame-major copy, 64 frames x the proposals per workgroup,
+    // results scattered into the full vectors
+    if (!sparse_reset)
+        EK_HIP(hipMemsetD32Async((hipDeviceptr_t)c->pam_vecs, 0x7f800000,
+                                 (size_t)count * c->n_pad, c->stream));
+    ek_launch_pam_list_dist(c->aos, c->G, c->A, c->act_list, n_act, c->pam_recs,
+                            count, c->pam_vecs, c->n_pad, c->stream);
+    EK_CHECK_LAUNCH();
+    c->pf.vecs.listed(n_act, count, sparse_reset);
+    ++c->pf.restricted;
+    // the list stays in c->amb until something else uses it: a window run
+    // right away may work from it (ek_pam_sparse.hip)
+    c->sp.ready = ek_sp_list_ok(slots, n_act);
+    c->sp.n_act = n_act;
+    *done = true;
+    return EK_OK;
+}
+
+// a pass over all frames per group of EK_PAM_GROUP proposals
+static int ek_pam_prefetch_full(ek_ctx *c, int count, bool prepared)
+{
+    c->pf.vecs.whole();
     const size_t rstride = ek_rec_bytes(c->A);
     for (int g0 = 0; g0 < count; g0 += EK_PAM_GROUP)
         ek_launch_pass_dist(std::min(count - g0, EK_PAM_GROUP), c->tiles, c->G,
@@ -712,26 +703,37 @@ static int ek_pam_prefetch_vectors(ek_ctx *c, int count, int32_t win_lo,
                             c->A, c->pam_recs + (size_t)g0 * rstride, c->pam_plan,
                             c->ctile, c->ctrace, c->stream, prepared && g0 == 0);
     EK_CHECK_LAUNCH();
-    ++c->pf_full;
+    ++c->pf.full;
     return EK_OK;
 }
 
-static int ek_pam_prefetch_frames(ek_ctx *c, const int64_t *frames, int32_t count,
-                                  int32_t win_lo, int32_t win_count);
-
-extern "C" int ek_pam_prefetch_window(ek_ctx *c, const int64_t *frames,
-                                      int32_t count, int32_t win_lo,
-                                      int32_t win_count)
+// The distance vectors of the `count` records in c->pam_recs.  When the state is
+// exact (every frame's distance is the distance to the medoid its label names)
+// and the window of clusters being worked through is known, only the frames a
+// proposal can touch get exact distances: the others get +inf.
+// local: the proposals are frames of this shard, proposal j for cluster
+// win_lo + j when win_count == count (the layout ek_pam_window_run expects)
+// prepared: ek_launch_pam_setup made the records (plan, candidate tile and the
+// cleared active-frame counter come with them)
+// *waited: the host waited for the stream on the way (the restricted form's read-back)
+static int ek_pam_prefetch_vectors(ek_ctx *c, int count, int32_t win_lo, int32_t win_count,
+                                   bool local, bool prepared = false, bool *waited = nullptr)
 {
-    if (c && (win_lo < 0 || win_count < 0 || win_lo + win_count > c->med_K))
-        return ek_fail(EK_EARG, "ek_pam_prefetch_window: clusters [%d,+%d) outside "
-                                "[0,%d)", win_lo, win_count, c->med_K);
-    return ek_pam_prefetch_frames(c, frames, count, win_lo, win_count);
-}
-
-extern "C" int ek_pam_prefetch(ek_ctx *c, const int64_t *frames, int32_t count)
-{
-    return ek_pam_prefetch_frames(c, frames, count, 0, 0);
+    if (waited)
+        *waited = false;
+    c->tab.invalidate();
+    c->sp.invalidate();
+    if (c->pf.form.try_restricted(c->prune, c->state_exact, c->A, win_count, c->n)) {
+        bool done = false;
+        int rc = ek_pam_prefetch_restricted(c, count, win_lo, win_count, local, prepared, &done);
+        if (rc)
+            return rc;
+        if (waited)
+            *waited = true;
+        if (done)
+            return EK_OK;
+    }
+    return ek_pam_prefetch_full(c, count, prepared);
 }
 
 static int ek_pam_prefetch_frames(ek_ctx *c, const int64_t *frames, int32_t count,
@@ -749,14 +751,12 @@ static int ek_pam_prefetch_frames(ek_ctx *c, const int64_t *frames, int32_t coun
             return ek_fail(EK_EARG, "ek_pam_prefetch: frame %lld out of range",
                            (long long)frames[j]);
     EK_HIP(hipSetDevice(c->device));
-    c->pf_count = 0;
+    c->pf.invalidate();
     if (count == 0)
         return EK_OK;
-    {
-        int rc = ek_pam_vecs_alloc(c);
-        if (rc)
-            return rc;
-    }
+    int rc = ek_pam_vecs_alloc(c);
+    if (rc)
+        return rc;
     const bool prepared = c->ctile != nullptr;
     if (prepared)
         ek_launch_pam_setup(c->aos, c->G, c->A, frames, count, c->goff, c->pam_recs,
@@ -765,17 +765,28 @@ static int ek_pam_prefetch_frames(ek_ctx *c, const int64_t *frames, int32_t coun
     else
         ek_launch_records_from_frames(c->aos, c->G, c->A, frames, count, c->goff,
                                       c->pam_recs, c->stream);
-    {
-        int rc = ek_pam_prefetch_vectors(c, count, win_lo, win_count, true,
-                                         prepared);
-        if (rc)
-            return rc;
-    }
+    rc = ek_pam_prefetch_vectors(c, count, win_lo, win_count, true, prepared);
+    if (rc)
+        return rc;
     for (int32_t j = 0; j < count; ++j)
-        c->pf_frames[j] = frames[j];
-    c->pf_count = count;
-    c->pf_external = false;
+        c->pf.frames[j] = frames[j];
+    c->pf.count = count;
+    c->pf.external = false;
     return EK_OK;
+}
+
+extern "C" int ek_pam_prefetch_window(ek_ctx *c, const int64_t *frames, int32_t count,
+                                      int32_t win_lo, int32_t win_count)
+{
+    if (c && (win_lo < 0 || win_count < 0 || win_lo + win_count > c->med_K))
+        return ek_fail(EK_EARG, "ek_pam_prefetch_window: clusters [%d,+%d) outside "
+                                "[0,%d)", win_lo, win_count, c->med_K);
+    return ek_pam_prefetch_frames(c, frames, count, win_lo, win_count);
+}
+
+extern "C" int ek_pam_prefetch(ek_ctx *c, const int64_t *frames, int32_t count)
+{
+    return ek_pam_prefetch_frames(c, frames, count, 0, 0);
 }
 
 // Round 5: the window's proposals without a wait of their own.  The selected frames
@@ -788,50 +799,39 @@ static int ek_pam_prefetch_frames(ek_ctx *c, const int64_t *frames, int32_t coun
 static int ek_pam_select_prefetch(ek_ctx *c, int32_t cid0, int32_t count,
                                   const int64_t *js, int32_t win_count, int64_t *frames)
 {
-    if (c->bat_cid0 != cid0 || count < 1 || count > c->bat_count)
+    if (!c->cnt.batch_covers(cid0, count))
         return ek_fail(EK_ESTATE, "ek_pam_sweep: member counts of clusters [%d,+%d) "
                                   "are not the ones at hand", cid0, count);
     EK_HIP(hipSetDevice(c->device));
     int rc = ek_pam_vecs_alloc(c);
     if (rc)
         return rc;
-    if (!c->sel_host)
-        EK_HIP(ek_pinned_malloc((void **)&c->sel_host, EK_PAM_WIN * sizeof(int64_t),
-                             hipHostMallocCoherent | hipHostMallocMapped));
     // (the drawn ranks are read by the selection from mapped host memory, the selected
-    // frames written into it: no copy either way)
-    int64_t *sel_dev_view = nullptr;
-    const int64_t *js_dev_view = nullptr;
-    if (c->pam_zero_copy) {
-        if (!c->js_host)
-            EK_HIP(ek_pinned_malloc((void **)&c->js_host, EK_PAM_WIN * sizeof(int64_t),
-                                 hipHostMallocCoherent | hipHostMallocMapped));
-        void *dp = nullptr, *dj = nullptr;
-        if (hipHostGetDevicePointer(&dp, c->sel_host, 0) == hipSuccess &&
-            hipHostGetDevicePointer(&dj, c->js_host, 0) == hipSuccess) {
-            sel_dev_view = (int64_t *)dp;
-            js_dev_view = (const int64_t *)dj;
-            for (int32_t j = 0; j < count; ++j)
-                c->js_host[j] = js[j];
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (!js_dev_view)
+    // frames written into it: no copy either way -- both, or neither)
+    int64_t *sel_view = nullptr, *js_view = nullptr;
+    rc = ek_mapped(&c->sel_host, EK_PAM_WIN, c->pam_zero_copy != 0, &sel_view);
+    if (!rc && c->pam_zero_copy)
+        rc = ek_mapped(&c->js_host, EK_PAM_WIN, true, &js_view);
+    if (rc)
+        return rc;
+    if (!sel_view || !js_view)
+        sel_view = js_view = nullptr;
+    for (int32_t j = 0; js_view && j < count; ++j)
+        c->js_host[j] = js[j];
+    if (!js_view)
         EK_HIP(hipMemcpyAsync(c->bat_sel + 2 * EK_PAM_WIN, js,
                               (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice,
                               c->stream));
     ek_launch_select_member_multi(c->assign, c->n, cid0, count, c->bat_scan,
-                                  js_dev_view ? js_dev_view : c->bat_sel + 2 * EK_PAM_WIN,
-                                  c->bat_sel + EK_PAM_WIN, c->stream, sel_dev_view);
+                                  js_view ? js_view : c->bat_sel + 2 * EK_PAM_WIN,
+                                  c->bat_sel + EK_PAM_WIN, c->stream, sel_view);
     EK_CHECK_LAUNCH();
-    if (!sel_dev_view)
+    if (!sel_view)
         EK_HIP(hipMemcpyAsync(c->sel_host, c->bat_sel + EK_PAM_WIN,
                               (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost,
                               c->stream));
-    c->bat_cid0 = -1;           // the scans describe the state at count time only
-    c->bat_count = 0;
-    c->pf_count = 0;
+    c->cnt.invalidate_batch();
+    c->pf.invalidate();
     ek_launch_pam_setup_dev(c->aos, c->G, c->A, c->bat_sel + EK_PAM_WIN, count, c->goff,
                             c->pam_recs, c->ctile, c->ctrace, c->pam_plan, c->amb_count + 3,
                             c->stream, c->dist, c->pam_dprop);
@@ -846,57 +846,37 @@ static int ek_pam_select_prefetch(ek_ctx *c, int32_t cid0, int32_t count,
         if (frames[j] < 0 || frames[j] >= c->n)
             return ek_fail(EK_EARG, "ek_pam_sweep: cluster %d has no member %lld",
                            cid0 + j, (long long)js[j]);
-        c->pf_frames[j] = frames[j];
+        c->pf.frames[j] = frames[j];
     }
-    c->pf_count = count;
-    c->pf_external = false;
+    c->pf.count = count;
+    c->pf.external = false;
     return EK_OK;
 }
 
-// The same window worked through by one workgroup (ek_pam_sparse.hip): possible
-// when the prefetch just made was restricted to a list of frames (still in
-// c->amb) and the window's tables are in place.  Enqueues; the caller reads the
-// window record back.
-static int ek_pam_window_sparse(ek_ctx *c, int32_t cid0, int32_t count,
-                                const int64_t *frames, const int64_t *n_members,
-                                int32_t win_count, EkSpArgs *args)
+// ---- a window of proposals decided on the device --------------------------------------
+// c->sp_buf: the slots' buckets | their lengths (at EK_SP_O_BCNT) | the records and lists
+// of the evaluation ahead (at EK_SP_O_SPEC, ek_sp_spec_bytes() of them)
+static constexpr size_t EK_SP_O_BCNT = (size_t)EK_PAM_WIN * EK_SP_CAP * sizeof(uint2);
+static constexpr size_t EK_SP_O_SPEC = EK_SP_O_BCNT + 256;
+
+// the one-workgroup window's arguments, all of them
+static EkSpArgs ek_sp_args(ek_ctx *c, int32_t cid0, int32_t count, const int64_t *frames,
+                           const int64_t *n_members, int32_t win_count, EkPamWin *win_host)
 {
-    const size_t cap = EK_SP_CAP;
-    const size_t o_bucket = 0;
-    const size_t o_bcnt = o_bucket + (size_t)EK_PAM_WIN * cap * sizeof(uint2);
-    const size_t o_spec = o_bcnt + 256;
-    if (!c->sp_buf) {
-        EK_HIP(ek_dev_malloc((void **)&c->sp_buf, o_spec + ek_sp_spec_bytes()));
-        c->sp_bcnt_clean = false;
-    }
-    if (c->pam_spec && !c->sp_marks) {
-        EK_HIP(ek_dev_malloc((void **)&c->sp_marks, (size_t)c->n * sizeof(unsigned long long)));
-        EK_HIP(hipMemsetAsync(c->sp_marks, 0, (size_t)c->n * sizeof(unsigned long long),
-                              c->stream));
-    }
-    const int K = c->med_K;
-    const size_t tb = (size_t)EK_PAM_WIN * (c->med_cap + 1);
-    // the state's cost tree, the slots' frames
-    ek_launch_pw_tree(c->dist, c->assign, c->n, c->pw_shapes, c->pw_n_full,
-                      c->pw_leaves, c->pw_chunks, c->sq_part, c->moved, c->stream);
-    ek_launch_sp_bucket(c->act_list, c->sp_nact, c->dist, c->assign, c->pam_vecs, c->n_pad,
-                        cid0, count, (uint2 *)(c->sp_buf + o_bucket),
-                        (unsigned int *)(c->sp_buf + o_bcnt), (int64_t)cap, c->stream,
-                        c->sp_bcnt_clean);
-    c->sp_bcnt_clean = false;
+    const size_t tb = ek_pam_tab_block(c);
     EkSpArgs a = {};
     a.dist = c->dist;
     a.assign = c->assign;
     a.n = c->n;
     a.n_total = (double)c->n;
     a.A = c->A;
-    a.K = K;
+    a.K = c->med_K;
     a.cid0 = cid0;
     a.count = count;
     a.win_count = win_count;
-    a.bucket = (const uint2 *)(c->sp_buf + o_bucket);
-    a.bcnt = (const unsigned int *)(c->sp_buf + o_bcnt);
-    a.bcap = (int64_t)cap;
+    a.bucket = (const uint2 *)c->sp_buf;
+    a.bcnt = (const unsigned int *)(c->sp_buf + EK_SP_O_BCNT);
+    a.bcap = (int64_t)EK_SP_CAP;
     for (int32_t i = 0; i < EK_PAM_WIN; ++i) {
         a.frames[i] = i < count ? frames[i] : 0;
         a.max_amb[i] = i < count ? n_members[i] : 0;
@@ -906,7 +886,7 @@ static int ek_pam_window_sparse(ek_ctx *c, int32_t cid0, int32_t count,
     a.med_aos = c->med_aos;
     a.med_G = c->med_G;
     a.med_idx = c->med_idx;
-    a.restore = c->pam_restore;
+    a.restore = c->tab.restore;
     a.frames_aos = c->aos;
     a.G = c->G;
     a.leaf = c->sq_part;
@@ -918,30 +898,25 @@ static int ek_pam_window_sparse(ek_ctx *c, int32_t cid0, int32_t count,
     a.max_pairs = c->sp_max_pairs;
     a.exact_always = c->sp_exact;
     a.win = c->pam_win_dev;
-    a.win_host = nullptr;
-    if (c->pam_zero_copy) {
-        void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, c->pam_win_host, 0) == hipSuccess)
-            a.win_host = (EkPamWin *)dp;
-        else
-            (void)hipGetLastError();
-    }
+    a.win_host = win_host;
     // every slot evaluated at once on the state the window opens with (not while a
     // rejected proposal's row of the medoid table is still to be put back)
-    a.use_spec = (c->pam_spec && c->pam_restore < 0 && count > 1) ? 1 : 0;
-    a.spec = (EkSpSpecRec *)(c->sp_buf + o_spec);
-    a.spec_lists = (uint32_t *)(c->sp_buf + o_spec + EK_PAM_WIN * sizeof(EkSpSpecRec));
+    a.use_spec = (c->pam_spec && c->tab.restore < 0 && count > 1) ? 1 : 0;
+    a.spec = (EkSpSpecRec *)(c->sp_buf + EK_SP_O_SPEC);
+    a.spec_lists = (uint32_t *)(c->sp_buf + EK_SP_O_SPEC + EK_PAM_WIN * sizeof(EkSpSpecRec));
     a.marks = c->sp_marks;
     a.finish_later = a.use_spec;
-    // (the vectors' reset rides in the finish kernel where every column written is one
-    // of the window's slots)
-    const bool reset_there = a.finish_later && c->vecs_rows == c->sp_nact &&
-                             c->vecs_cols == count;
     a.act_list = c->act_list;
-    a.n_act = c->sp_nact;
+    a.n_act = c->sp.n_act;
     a.n_pad = c->n_pad;
-    a.vecs = reset_there ? c->pam_vecs : nullptr;
+    a.vecs = c->pf.vecs.reset_there(a.finish_later, c->sp.n_act, count) ? c->pam_vecs : nullptr;
+    return a;
+}
+
 #ifdef EK_SP_PROF
+// measurement builds: the window kernel's 10 ns ticks per step, printed every 100 windows
+static int ek_sp_prof(ek_ctx *c, EkSpArgs *a)
+{
     static unsigned long long *prof_dev = nullptr;
     static unsigned long long prof_tot[16];
     static int prof_n = 0;
@@ -949,7 +924,7 @@ static int ek_pam_window_sparse(ek_ctx *c, int32_t cid0, int32_t count,
         EK_HIP(ek_dev_malloc((void **)&prof_dev, 16 * sizeof(unsigned long long)));
         EK_HIP(hipMemset(prof_dev, 0, 16 * sizeof(unsigned long long)));
     }
-    a.prof = prof_dev;
+    a->prof = prof_dev;
     if (++prof_n % 100 == 0) {
         EK_HIP(ek_wait(c));
         EK_HIP(hipMemcpy(prof_tot, prof_dev, sizeof(prof_tot), hipMemcpyDeviceToHost));
@@ -962,48 +937,67 @@ static int ek_pam_window_sparse(ek_ctx *c, int32_t cid0, int32_t count,
                 prof_tot[6] * 1e-2 / prof_n, prof_tot[7] * 1e-2 / prof_n,
                 prof_tot[0] * 1e-2 / prof_n, prof_tot[9] * 1e-2 / prof_n);
     }
+    return EK_OK;
+}
+#endif
+
+// The window worked through by one workgroup (ek_pam_sparse.hip): possible when the
+// prefetch just made was restricted to a list of frames (still in c->amb) and the
+// window's tables are in place.  Enqueues; the caller reads the window record back.
+static int ek_pam_window_one_wg(ek_ctx *c, int32_t cid0, int32_t count, const int64_t *frames,
+                                const int64_t *n_members, int32_t win_count, EkSpArgs *args)
+{
+    if (!c->sp_buf) {
+        EK_HIP(ek_dev_malloc((void **)&c->sp_buf, EK_SP_O_SPEC + ek_sp_spec_bytes()));
+        c->sp.bcnt_clean = false;
+    }
+    if (c->pam_spec && !c->sp_marks) {
+        EK_HIP(ek_dev_malloc((void **)&c->sp_marks, (size_t)c->n * sizeof(unsigned long long)));
+        EK_HIP(hipMemsetAsync(c->sp_marks, 0, (size_t)c->n * sizeof(unsigned long long),
+                              c->stream));
+    }
+    // the state's cost tree, the slots' frames
+    ek_launch_pw_tree(c->dist, c->assign, c->n, c->pw_shapes, c->pw_n_full,
+                      c->pw_leaves, c->pw_chunks, c->sq_part, c->moved, c->stream);
+    ek_launch_sp_bucket(c->act_list, c->sp.n_act, c->dist, c->assign, c->pam_vecs, c->n_pad,
+                        cid0, count, (uint2 *)c->sp_buf,
+                        (unsigned int *)(c->sp_buf + EK_SP_O_BCNT), (int64_t)EK_SP_CAP,
+                        c->stream, c->sp.bcnt_clean);
+    c->sp.bcnt_clean = false;
+    EkPamWin *win_host = nullptr;
+    int rc = ek_mapped(&c->pam_win_host, 1, c->pam_zero_copy != 0, &win_host);
+    if (rc)
+        return rc;
+    EkSpArgs a = ek_sp_args(c, cid0, count, frames, n_members, win_count, win_host);
+#ifdef EK_SP_PROF
+    rc = ek_sp_prof(c, &a);
+    if (rc)
+        return rc;
 #endif
     if (a.use_spec)
         ek_launch_sp_spec(a, c->stream);
     ek_launch_sp_window(a, c->stream);
     EK_CHECK_LAUNCH();
     *args = a;
-    c->pam_restore = -1;
-    c->sp_ready = false;
-    c->pf_hits += count;
-    ++c->sp_windows;
+    c->tab.restore = -1;
+    c->sp.invalidate();
+    c->pf.hits += count;
+    ++c->sp.windows;
     return EK_OK;
 }
 
-// A window of proposals without a host round trip each (reference
-// kmedoids.py:575-699 for clusters cid0 .. cid0 + count - 1, in order).  frames[i]
-// is the frame proposed for cluster cid0 + i -- the caller drew it from the
-// member list as it stood when the window was opened -- and n_members[i] that
-// list's length; all of them must have been prefetched (ek_pam_prefetch_window).
-// Every proposal's kernels are enqueued at once; the device decides each
-// (mean of squares, float64, strict <), commits or undoes it, and stops the
-// window at the first cluster whose membership an accepted proposal changed:
-// *n_done slots were decided, the caller handles slot *n_done one at a time
-// (its member list has to be counted again) and opens a new window after it.
-// next_count > 0: the member counts of clusters next_cid0 .. +next_count (what the
-// window after this one starts with) are taken on the state this window leaves,
-// right behind its kernels, and come back with its record -- one wait less per
-// window; they stand if the window runs to its end (the caller checks)
-static int ek_pam_window_run_impl(ek_ctx *c, int32_t cid0, int32_t count,
-                                  const int64_t *frames, const int64_t *n_members,
-                                  int32_t win_lo, int32_t win_count,
-                                  int32_t *n_done, int32_t *accept,
-                                  double *old_cost, double *new_cost,
-                                  int64_t *n_ambiguous, int32_t next_cid0,
-                                  int32_t next_count, int64_t *next_counts)
+// the window's arguments checked; newd[i]: slot i's prefetched vector, *max_m: the
+// longest member list
+static int ek_pam_window_validate(ek_ctx *c, int32_t cid0, int32_t count, const int64_t *frames,
+                                  const int64_t *n_members, int32_t win_lo, int32_t win_count,
+                                  bool outputs, const float **newd, int64_t *max_m)
 {
     int rc = ek_pam_precheck(c, cid0, "ek_pam_window_run");
     if (rc)
         return rc;
-    if (count < 1 || count > EK_PAM_WIN || cid0 + count > c->med_K || !frames ||
-        !n_members || !n_done || !accept)
-        return ek_fail(EK_EARG, "ek_pam_window_run: bad window [%d,+%d)", cid0,
-                       count);
+    if (count < 1 || count > EK_PAM_WIN || cid0 + count > c->med_K || !frames || !n_members ||
+        !outputs)
+        return ek_fail(EK_EARG, "ek_pam_window_run: bad window [%d,+%d)", cid0, count);
     // bit i of a proposal's moved-cluster mask is cluster win_lo + i, and the
     // device reads it as slot i of this run
     if (win_lo != cid0 || win_count < count || win_count > 32)
@@ -1014,8 +1008,7 @@ static int ek_pam_window_run_impl(ek_ctx *c, int32_t cid0, int32_t count,
         return ek_fail(EK_ESTATE, "ek_pam_window_run: the pairwise-sum shape of a "
                                   "full chunk is not the expected perfect tree");
     EK_HIP(hipSetDevice(c->device));
-    int64_t max_m = 0;
-    const float *newd[EK_PAM_WIN];
+    *max_m = 0;
     for (int32_t i = 0; i < count; ++i) {
         if (frames[i] < 0 || frames[i] >= c->n || n_members[i] < 0 ||
             n_members[i] > c->n)
@@ -1026,43 +1019,45 @@ static int ek_pam_window_run_impl(ek_ctx *c, int32_t cid0, int32_t count,
         if (!newd[i])
             return ek_fail(EK_ESTATE, "ek_pam_window_run: frame %lld was not "
                                       "prefetched", (long long)frames[i]);
-        max_m = std::max(max_m, n_members[i]);
+        *max_m = std::max(*max_m, n_members[i]);
     }
-    // (a window that had to hand a proposal back -- more ambiguous members x
-    // medoids within reach than one workgroup should search -- cost a window's
-    // set-up for one slot: the next few go the three-launch way, twice as many
-    // each time it happens again)
-    if (c->sp_backoff > 0)
-        --c->sp_backoff;
-    bool sparse = c->pam_sparse && c->sp_ready && c->tab_lo == cid0 &&
-                  count <= c->tab_n && c->prune && c->state_exact && c->A >= 3 &&
-                  c->aos != nullptr && c->pw_chunks <= EK_SP_MAX_CHUNKS &&
-                  c->pw_leaves <= EK_SP_MAX_CHUNKS * EK_PW_FULL_LEAVES &&
-                  (c->sp_backoff == 0 || c->sp_max_pairs == 0);
-    for (int32_t i = 0; sparse && i < count; ++i)
-        sparse = newd[i] == c->pam_vecs + (size_t)i * c->n_pad;
-    EkSpArgs sp_args = {};
-    if (sparse) {
-        rc = ek_pam_window_sparse(c, cid0, count, frames, n_members, win_count, &sp_args);
-        if (rc)
-            return rc;
-    } else {
-        rc = ek_pam_amb_room(c, max_m);  // may synchronise: before anything is enqueued
-        if (rc)
-            return rc;
-    }
+    return EK_OK;
+}
+
+// one workgroup, or three launches per slot?  (a window has gone by for the wait)
+static bool ek_pam_window_form(ek_ctx *c, int32_t cid0, int32_t count, const float *const *newd)
+{
+    const bool wait_over = c->sp.wait.over(c->sp_max_pairs);
+    bool columns = true;
+    for (int32_t i = 0; columns && i < count; ++i)
+        columns = newd[i] == c->pam_vecs + (size_t)i * c->n_pad;
+    return ek_sp_eligible(c->pam_sparse != 0, c->sp.ready,
+                          ek_pam_tables_cover(c->tab.lo, c->tab.n, cid0, count),
+                          ek_pam_prune_ok(c->prune, c->state_exact, c->A), c->aos != nullptr,
+                          c->pw_chunks, c->pw_leaves, wait_over, columns);
+}
+
+// Three launches per slot (ek_pam_tail), every slot's enqueued at once; then the last
+// slot's trial state, if accepted.
+static int ek_pam_window_slots(ek_ctx *c, int32_t cid0, int32_t count, const int64_t *frames,
+                               const int64_t *n_members, const float *const *newd,
+                               int64_t max_m, int32_t win_count)
+{
+    int rc = ek_pam_amb_room(c, max_m);  // may synchronise: before anything is enqueued
+    if (rc)
+        return rc;
     const int K = c->med_K;
-    for (int32_t i = 0; !sparse && i < count; ++i) {
+    for (int32_t i = 0; i < count; ++i) {
         const int32_t cid = cid0 + i;
         // the first proposal's trial table (and the window record: `count`
         // slots, nothing decided); the others' are set up by the last workgroup
         // of the proposal before
         if (i == 0)
             ek_launch_pam_trial(c->tiles, c->G, c->A, c->med_aos, c->med_G, K, cid,
-                                c->pam_restore, frames[i], nullptr, nullptr,
+                                c->tab.restore, frames[i], nullptr, nullptr,
                                 nullptr, c->amb_count, c->moved, c->stream,
                                 c->pam_win_dev, count);
-        c->pam_restore = -1;
+        c->tab.restore = -1;
         const bool more = i + 1 < count;
         EkPamDecide dc;
         dc.win = c->pam_win_dev;
@@ -1082,86 +1077,89 @@ static int ek_pam_window_run_impl(ek_ctx *c, int32_t cid0, int32_t count,
         dc.G = c->G;
         dc.amb_count = c->amb_count;
         dc.moved = c->moved;
-        rc = ek_pam_tail(c, cid, newd[i], n_members[i], win_lo, win_count,
+        rc = ek_pam_tail(c, cid, newd[i], n_members[i], cid0, win_count,
                          &c->pam_win_dev->out[i], &dc,
                          i > 0 ? &c->pam_win_dev->accept[i - 1] : &c->pam_win_dev->pad);
         if (rc)
             return rc;
-        ++c->pf_hits;
+        ++c->pf.hits;
     }
-    // the last slot's trial state, if accepted (the others were taken over by
-    // the classification of the slot after them)
-    if (!sparse)
-        ek_launch_pam_apply(&c->pam_win_dev->accept[count - 1], c->dist, c->ndist,
-                            c->assign, c->nassign, c->n, c->stream);
+    // (the others were taken over by the classification of the slot after them)
+    ek_launch_pam_apply(&c->pam_win_dev->accept[count - 1], c->dist, c->ndist,
+                        c->assign, c->nassign, c->n, c->stream);
     EK_CHECK_LAUNCH();
-    // (the window's kernel and the scan write their results into mapped host memory
-    // themselves where they can: a copy kernel each, in the chain the host waits for)
-    if (!(sparse && sp_args.win_host))
-        EK_HIP(hipMemcpyAsync(c->pam_win_host, c->pam_win_dev, sizeof(EkPamWin),
+    return EK_OK;
+}
+
+// The member counts of clusters next_cid0 .. +next_count, taken on the state the window
+// leaves, right behind its kernels: into mapped host memory (*view) or copied back.
+static int ek_pam_window_next_counts(ek_ctx *c, int32_t next_cid0, int32_t next_count,
+                                     int64_t *next_counts, int64_t **view)
+{
+    *view = nullptr;
+    if (next_count <= 0)
+        return EK_OK;
+    if (c->pam_zero_copy) {
+        int rc = ek_mapped(&c->cnt_host, EK_PAM_WIN, true, view);
+        if (rc)
+            return rc;
+    }
+    ek_launch_count_members_multi(c->assign, c->n, next_cid0, next_count,
+                                  c->bat_blockcnt, c->bat_scan, c->bat_sel, c->stream,
+                                  *view);
+    EK_CHECK_LAUNCH();
+    if (!*view)
+        EK_HIP(hipMemcpyAsync(next_counts, c->bat_sel,
+                              (size_t)next_count * sizeof(int64_t),
                               hipMemcpyDeviceToHost, c->stream));
-    int64_t *cnt_dev_view = nullptr;
-    if (next_count > 0) {
-        if (c->pam_zero_copy) {
-            if (!c->cnt_host)
-                EK_HIP(ek_pinned_malloc((void **)&c->cnt_host, EK_PAM_WIN * sizeof(int64_t),
-                                     hipHostMallocCoherent | hipHostMallocMapped));
-            void *dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, c->cnt_host, 0) == hipSuccess)
-                cnt_dev_view = (int64_t *)dp;
-            else
-                (void)hipGetLastError();
-        }
-        ek_launch_count_members_multi(c->assign, c->n, next_cid0, next_count,
-                                      c->bat_blockcnt, c->bat_scan, c->bat_sel, c->stream,
-                                      cnt_dev_view);
-        EK_CHECK_LAUNCH();
-        if (!cnt_dev_view)
-            EK_HIP(hipMemcpyAsync(next_counts, c->bat_sel,
-                                  (size_t)next_count * sizeof(int64_t),
-                                  hipMemcpyDeviceToHost, c->stream));
-    }
-    if (sparse && sp_args.finish_later) {
-        // the accepted proposals' rows of the medoid table and the slots' marks: behind
-        // what the host waits for
-        if (!c->win_ev)
-            EK_HIP(ek_event_create_flags(&c->win_ev, hipEventDisableTiming));
-        EK_HIP(hipEventRecord(c->win_ev, c->stream));
-        ek_launch_sp_finish(sp_args, c->stream);
-        EK_CHECK_LAUNCH();
-        c->sp_bcnt_clean = sp_args.count == EK_PAM_WIN;  // (all of the lengths)
-        for (;;) {
-            const hipError_t e = hipEventQuery(c->win_ev);
-            if (e == hipSuccess)
-                break;
-            if (e != hipErrorNotReady)
-                return ek_fail(EK_EHIP, "ek_pam_window_run: %s", hipGetErrorString(e));
-        }
-    } else {
+    return EK_OK;
+}
+
+// The host's one wait of a window: for the stream, or -- sp: a one-workgroup window
+// whose finish kernel comes later -- for the event in front of that kernel (the accepted
+// proposals' rows of the medoid table and the slots' marks: behind what the host waits
+// for).
+static int ek_pam_window_wait(ek_ctx *c, const EkSpArgs *sp)
+{
+    if (!sp || !sp->finish_later) {
         EK_HIP(ek_wait(c));
+        return EK_OK;
     }
-    c->bat_cid0 = -1;
-    c->bat_count = 0;
-    if (cnt_dev_view)
-        for (int32_t i = 0; i < next_count; ++i)
-            next_counts[i] = c->cnt_host[i];
+    if (!c->win_ev)
+        EK_HIP(ek_event_create_flags(&c->win_ev, hipEventDisableTiming));
+    EK_HIP(hipEventRecord(c->win_ev, c->stream));
+    ek_launch_sp_finish(*sp, c->stream);
+    EK_CHECK_LAUNCH();
+    c->sp.bcnt_clean = sp->count == EK_PAM_WIN;     // (all of the lengths)
+    for (;;) {
+        const hipError_t e = hipEventQuery(c->win_ev);
+        if (e == hipSuccess)
+            return EK_OK;
+        if (e != hipErrorNotReady)
+            return ek_fail(EK_EHIP, "ek_pam_window_run: %s", hipGetErrorString(e));
+    }
+}
+
+// The record is on the host: what it says about the context's state, then the caller's
+// outputs.  sp: the window was one workgroup's.
+static int ek_pam_window_account(ek_ctx *c, int32_t cid0, int32_t count, const int64_t *n_members,
+                                 const EkSpArgs *sp, int32_t *n_done, int32_t *accept,
+                                 double *old_cost, double *new_cost, int64_t *n_ambiguous)
+{
     const EkPamWin &w = *c->pam_win_host;
-    if (sparse && sp_args.finish_later && sp_args.vecs && w.stop == count) {
-        c->vecs_rows = 0;       // (ek_sp_finish_kernel has put the vectors back to +inf)
-        c->pf_count = 0;        //  ... nothing of them is a prefetched vector any more
-    }
-    c->tab_n = 0;            // the medoid table has moved on
+    if (c->pf.vecs.finished(sp && sp->finish_later && sp->vecs, w.stop, count))
+        c->pf.invalidate();
+    c->tab.invalidate();
     c->pam_cid = -1;
-    c->cnt_cid = -1;
-    c->pf_hits -= count - w.stop;       // the slots past the stop were not served
-    if (sparse) {
-        c->sp_ahead += w.pad >> 8;      // slots taken over as evaluated ahead
-        if (w.pad & 0xff) {
-            ++c->sp_bailed;
-            c->sp_backoff = c->sp_backoff_next;
-            c->sp_backoff_next = std::min(256, 2 * c->sp_backoff_next);
+    c->cnt.invalidate_one();
+    c->pf.hits -= count - w.stop;       // the slots past the stop were not served
+    if (sp) {
+        c->sp.ahead += w.pad >> 8;      // slots taken over as evaluated ahead
+        if (w.pad & 0xff) {             // a proposal handed back
+            ++c->sp.bailed;
+            c->sp.wait.handed_back();
         } else {
-            c->sp_backoff_next = 8;
+            c->sp.wait.clean();
         }
     }
     if (w.err)
@@ -1178,60 +1176,78 @@ static int ek_pam_window_run_impl(ek_ctx *c, int32_t cid0, int32_t count,
         if (n_ambiguous)
             n_ambiguous[i] = w.out[i].n_amb;
     }
-    if (next_count > 0 && w.stop == count) {
-        // the state the counts were taken on is the one the next window opens with
-        c->bat_cid0 = next_cid0;
-        c->bat_count = next_count;
-    }
     return EK_OK;
 }
 
-extern "C" int ek_pam_window_run(ek_ctx *c, int32_t cid0, int32_t count,
-                                 const int64_t *frames, const int64_t *n_members,
-                                 int32_t win_lo, int32_t win_count,
-                                 int32_t *n_done, int32_t *accept,
-                                 double *old_cost, double *new_cost,
-                                 int64_t *n_ambiguous)
+// A window of proposals without a host round trip each (reference
+// kmedoids.py:575-699 for clusters cid0 .. cid0 + count - 1, in order).  frames[i]
+// is the frame proposed for cluster cid0 + i -- the caller drew it from the
+// member list as it stood when the window was opened -- and n_members[i] that
+// list's length; all of them must have been prefetched (ek_pam_prefetch_window).
+// Every proposal's kernels are enqueued at once; the device decides each
+// (mean of squares, float64, strict <), commits or undoes it, and stops the
+// window at the first cluster whose membership an accepted proposal changed:
+// *n_done slots were decided, the caller handles slot *n_done one at a time
+// (its member list has to be counted again) and opens a new window after it.
+// next_count > 0: the member counts of clusters next_cid0 .. +next_count (what the
+// window after this one starts with) are taken on the state this window leaves,
+// right behind its kernels, and come back with its record -- one wait less per
+// window; they stand if the window runs to its end (the caller checks)
+static int ek_pam_window_run_impl(ek_ctx *c, int32_t cid0, int32_t count, const int64_t *frames,
+                                  const int64_t *n_members, int32_t win_lo, int32_t win_count,
+                                  int32_t *n_done, int32_t *accept, double *old_cost,
+                                  double *new_cost, int64_t *n_ambiguous, int32_t next_cid0,
+                                  int32_t next_count, int64_t *next_counts)
 {
-    return ek_pam_window_run_impl(c, cid0, count, frames, n_members, win_lo, win_count,
-                                  n_done, accept, old_cost, new_cost, n_ambiguous, 0, 0,
-                                  nullptr);
+    const float *newd[EK_PAM_WIN];
+    int64_t max_m = 0;
+    int rc = ek_pam_window_validate(c, cid0, count, frames, n_members, win_lo, win_count,
+                                    n_done && accept, newd, &max_m);
+    if (rc)
+        return rc;
+    const bool sparse = ek_pam_window_form(c, cid0, count, newd);
+    EkSpArgs sp_args = {};
+    const EkSpArgs *sp = sparse ? &sp_args : nullptr;
+    rc = sparse ? ek_pam_window_one_wg(c, cid0, count, frames, n_members, win_count, &sp_args)
+                : ek_pam_window_slots(c, cid0, count, frames, n_members, newd, max_m, win_count);
+    if (rc)
+        return rc;
+    // (the window's kernel and the scan write their results into mapped host memory
+    // themselves where they can: a copy kernel each, in the chain the host waits for)
+    if (!(sp && sp->win_host))
+        EK_HIP(hipMemcpyAsync(c->pam_win_host, c->pam_win_dev, sizeof(EkPamWin),
+                              hipMemcpyDeviceToHost, c->stream));
+    int64_t *cnt_view = nullptr;
+    rc = ek_pam_window_next_counts(c, next_cid0, next_count, next_counts, &cnt_view);
+    if (rc)
+        return rc;
+    rc = ek_pam_window_wait(c, sp);
+    if (rc)
+        return rc;
+    c->cnt.invalidate_batch();
+    for (int32_t i = 0; cnt_view && i < next_count; ++i)
+        next_counts[i] = c->cnt_host[i];
+    rc = ek_pam_window_account(c, cid0, count, n_members, sp, n_done, accept, old_cost,
+                               new_cost, n_ambiguous);
+    // the state the counts were taken on is the one the next window opens with
+    if (!rc && next_count > 0 && *n_done == count)
+        c->cnt.batch(next_cid0, next_count);
+    return rc;
+}
+
+extern "C" int ek_pam_window_run(ek_ctx *c, int32_t cid0, int32_t count, const int64_t *frames,
+                                 const int64_t *n_members, int32_t win_lo, int32_t win_count,
+                                 int32_t *n_done, int32_t *accept, double *old_cost,
+                                 double *new_cost, int64_t *n_ambiguous)
+{
+    return ek_pam_window_run_impl(c, cid0, count, frames, n_members, win_lo, win_count, n_done,
+                                  accept, old_cost, new_cost, n_ambiguous, 0, 0, nullptr);
 }
 
 // ---- a whole sweep's window loop on the host side of the library ------------------------
-// numpy's legacy RandomState.choice(m) / randint(0, m): 32-bit outputs of the
-// Mersenne Twister masked to the bits of m - 1, values above it rejected; m == 1
-// consumes nothing.  `raw` are such outputs, *pos the next unused one.
-// -> 0: drawn, 1: the outputs ran out (nothing consumed)
-static int ek_draw_at(const uint32_t *raw, int64_t n_raw, int64_t *pos, int64_t m,
-                      int64_t *out)
-{
-    const uint64_t rng = (uint64_t)(m - 1);
-    if (rng == 0) {
-        *out = 0;
-        return 0;
-    }
-    uint64_t mask = rng;
-    mask |= mask >> 1;
-    mask |= mask >> 2;
-    mask |= mask >> 4;
-    mask |= mask >> 8;
-    mask |= mask >> 16;
-    int64_t p = *pos;
-    for (;;) {
-        if (p >= n_raw)
-            return 1;
-        const uint64_t v = raw[p++] & mask;
-        if (v <= rng) {
-            *out = (int64_t)v;
-            *pos = p;
-            return 0;
-        }
-    }
-}
-
-// The draws above, exposed for tests that hold them against numpy itself (no
-// device involved): out[i] = RandomState.choice(m[i]) taken from `raw` at *pos on.
+// numpy's draws (ek_draw_at, ek_pam_policy.h), exposed for tests that hold them against
+// numpy itself (no device involved): out[i] = RandomState.choice(m[i]) taken from `raw`
+// at *pos on.
 // -> how many were made (fewer than count: the outputs ran out, or m[i] < 1)
 extern "C" int64_t ek_np_choice_draws(const uint32_t *raw, int64_t n_raw, int64_t *pos,
                                       const int64_t *m, int64_t count, int64_t *out)
@@ -1246,6 +1262,149 @@ extern "C" int64_t ek_np_choice_draws(const uint32_t *raw, int64_t n_raw, int64_
             break;
     }
     return i;
+}
+
+// what a sweep is given and gives back, cluster by cluster
+struct EkSweep {
+    int32_t K, width;
+    const uint32_t *raw;        // the next outputs of the caller's RandomState
+    int64_t n_raw, *pos;        // ... how many the draws made so far have consumed
+    const int64_t *proposals;   // or the proposals themselves: nothing is drawn
+    int64_t *medoids;
+    int32_t *accept;
+    double *old_cost, *new_cost;
+    int64_t *n_amb;
+    void note(int32_t cid, int a, double o, double nw, int64_t amb, int64_t frame) const
+    {
+        accept[cid] = a;
+        old_cost[cid] = o;
+        new_cost[cid] = nw;
+        n_amb[cid] = amb;
+        if (a)
+            medoids[cid] = frame;
+    }
+};
+
+// A window's proposals: the draws the real stream will produce if the counts still hold
+// when each cluster's turn comes (up to the first empty cluster), or the caller's;
+// selected and prefetched.  -> *n_slots of them; *status = 1: the outputs ran out
+static int ek_sweep_open(ek_ctx *c, const EkSweep &s, int32_t cid, int32_t cnt,
+                         const int64_t *counts, int64_t *js, int64_t *frames,
+                         int32_t *n_slots, int32_t *status)
+{
+    int32_t n = 0;
+    if (!s.proposals) {
+        int64_t p = *s.pos;
+        for (; n < cnt && counts[n] > 0; ++n)
+            if (ek_draw_at(s.raw, s.n_raw, &p, counts[n], &js[n])) {
+                *status = 1;
+                return EK_OK;
+            }
+    } else {
+        n = cnt;
+        for (int32_t i = 0; i < cnt; ++i)
+            frames[i] = s.proposals[cid + i];
+    }
+    *n_slots = n;
+    int rc = EK_OK;
+    // (drawn proposals are members of their clusters: see ek_pam_prefetch_restricted)
+    c->pf.members = !s.proposals;
+    if (!s.proposals && n > 0 && c->ctile)
+        rc = ek_pam_select_prefetch(c, cid, n, js, cnt, frames);
+    else {
+        if (!s.proposals && n > 0)
+            rc = ek_pam_select_members_batch(c, cid, n, js, frames);
+        if (!rc)
+            rc = ek_pam_prefetch_window(c, frames, n, cid, cnt);
+    }
+    c->pf.members = false;
+    return rc;
+}
+
+// The cluster a window stopped at: its members changed under an accepted proposal (or
+// it is empty) -- counted and drawn now, one proposal on its own.
+// *status = 1: the outputs ran out; 2: the cluster has no member
+static int ek_sweep_single(ek_ctx *c, const EkSweep &s, int32_t cid, int32_t *status)
+{
+    int64_t prop = -1, amb = 0;
+    double o = 0.0, nw = 0.0;
+    int rc;
+    if (!s.proposals) {
+        int64_t m = 0, j = 0;
+        rc = ek_pam_count_members(c, cid, &m);
+        if (rc)
+            return rc;
+        if (m <= 0) {
+            *status = 2;
+            return EK_OK;
+        }
+        if (ek_draw_at(s.raw, s.n_raw, s.pos, m, &j)) {
+            *status = 1;
+            return EK_OK;
+        }
+        rc = ek_pam_propose_member(c, cid, j, &prop, &o, &nw, &amb);
+    } else {
+        prop = s.proposals[cid];
+        rc = ek_pam_propose(c, cid, prop, &o, &nw, &amb);
+    }
+    if (rc)
+        return rc;
+    const int a = nw < o;                               // kmedoids.py:683
+    rc = ek_pam_commit(c, a);
+    if (rc)
+        return rc;
+    s.note(cid, a, o, nw, amb, prop);
+    return EK_OK;
+}
+
+// One window of the sweep, from cluster *cid on: its counts, its proposals, the run, the
+// real draws behind the slots decided, the cluster it stopped at.  `ahead`: the counts
+// that rode along with the window before, *have_counts: they are this window's.
+static int ek_sweep_window(ek_ctx *c, const EkSweep &s, int32_t *cid_io, int64_t *ahead,
+                           bool *have_counts, int32_t *status)
+{
+    const int32_t cid = *cid_io;
+    const EkSweepWin win(cid, s.K, s.width);
+    int64_t counts[EK_PAM_WIN], js[EK_PAM_WIN], frames[EK_PAM_WIN], na[EK_PAM_WIN];
+    int32_t acc[EK_PAM_WIN];
+    double oc[EK_PAM_WIN], nc[EK_PAM_WIN];
+    int rc = EK_OK;
+    if (*have_counts && c->cnt.bat_cid0 == cid && c->cnt.bat_count == win.cnt)
+        std::copy(ahead, ahead + win.cnt, counts);
+    else
+        rc = ek_pam_count_members_batch(c, cid, win.cnt, counts);
+    *have_counts = false;
+    if (rc)
+        return rc;
+    int32_t n_slots = 0, n_done = 0;
+    rc = ek_sweep_open(c, s, cid, win.cnt, counts, js, frames, &n_slots, status);
+    if (rc || *status)
+        return rc;
+    if (n_slots > 0) {
+        const int32_t ncnt = win.ride_along(n_slots, s.K, s.width);
+        rc = ek_pam_window_run_impl(c, cid, n_slots, frames, counts, cid, win.cnt, &n_done,
+                                    acc, oc, nc, na, win.hi, ncnt, ahead);
+        if (rc)
+            return rc;
+        *have_counts = ek_sweep_counts_stand(ncnt, n_done, n_slots);
+    }
+    for (int32_t i = 0; i < n_done; ++i) {
+        // the real draws, in order: the member lists are the ones the
+        // guesses were drawn from, so they are the same draws
+        int64_t j = -1;
+        if (!s.proposals && (ek_draw_at(s.raw, s.n_raw, s.pos, counts[i], &j) || j != js[i]))
+            return ek_fail(EK_ESTATE, "ek_pam_sweep: draw %lld for cluster %d, "
+                                      "guessed %lld", (long long)j, cid + i,
+                           (long long)js[i]);
+        s.note(cid + i, acc[i], oc[i], nc[i], na[i], frames[i]);
+    }
+    *cid_io = cid + n_done;
+    if (*cid_io < win.hi) {
+        rc = ek_sweep_single(c, s, *cid_io, status);
+        if (!rc && !*status)
+            ++*cid_io;
+    }
+    return rc;
 }
 
 // The loop of kmedoids.py:575-699 over clusters *cid .. K - 1 in windows of up to
@@ -1278,128 +1437,21 @@ extern "C" int ek_pam_sweep(ek_ctx *c, int32_t K, int32_t width, const uint32_t 
                        (long long)*pos);
     if (n_raw > 0 && (uint64_t)c->n > 0xffffffffull)
         return ek_fail(EK_EARG, "ek_pam_sweep: member lists of 2**32 frames and more");
-    int32_t cid = *cid_io;
-    *status = 0;
-    int64_t counts[EK_PAM_WIN], js[EK_PAM_WIN], frames[EK_PAM_WIN], na[EK_PAM_WIN];
-    int32_t acc[EK_PAM_WIN];
-    double oc[EK_PAM_WIN], nc[EK_PAM_WIN];
+    const EkSweep s = {K, width, raw, n_raw, pos, proposals, medoids, accept,
+                       old_cost, new_cost, n_amb};
     int64_t ahead[EK_PAM_WIN];
-    bool have_counts = false;       // `ahead` holds the counts of the window at `cid`
-    while (cid < K) {
-        const int32_t hi = std::min(K, cid + width), cnt = hi - cid;
-        int rc = EK_OK;
-        if (have_counts && c->bat_cid0 == cid && c->bat_count == cnt) {
-            for (int32_t s = 0; s < cnt; ++s)
-                counts[s] = ahead[s];
-        } else {
-            rc = ek_pam_count_members_batch(c, cid, cnt, counts);
-        }
-        have_counts = false;
+    bool have_counts = false;       // `ahead` holds the counts of the window at *cid_io
+    *status = 0;
+    int32_t cid = *cid_io;
+    while (cid < K && !*status) {
+        int rc = ek_sweep_window(c, s, &cid, ahead, &have_counts, status);
         if (rc)
             return rc;
-        int32_t n_slots = 0;
-        if (!proposals) {
-            // the draws the real stream will produce if these counts still hold
-            // when each cluster's turn comes
-            int64_t p = *pos;
-            for (; n_slots < cnt && counts[n_slots] > 0; ++n_slots)
-                if (ek_draw_at(raw, n_raw, &p, counts[n_slots], &js[n_slots])) {
-                    *cid_io = cid;
-                    *status = 1;
-                    return EK_OK;
-                }
-        } else {
-            n_slots = cnt;
-            for (int32_t s = 0; s < cnt; ++s)
-                frames[s] = proposals[cid + s];
-        }
-        // (drawn proposals are members of their clusters: see ek_pam_prefetch_vectors)
-        c->pf_members = !proposals;
-        if (!proposals && n_slots > 0 && c->ctile)
-            rc = ek_pam_select_prefetch(c, cid, n_slots, js, cnt, frames);
-        else {
-            if (!proposals && n_slots > 0)
-                rc = ek_pam_select_members_batch(c, cid, n_slots, js, frames);
-            if (!rc)
-                rc = ek_pam_prefetch_window(c, frames, n_slots, cid, cnt);
-        }
-        c->pf_members = false;
-        if (rc)
-            return rc;
-        int32_t n_done = 0;
-        if (n_slots > 0) {
-            // (the counts the next window starts with ride along when this one
-            // covers its clusters: they stand if it runs to its end)
-            const int32_t ncnt = (n_slots == cnt) ? std::min(K, hi + width) - hi : 0;
-            rc = ek_pam_window_run_impl(c, cid, n_slots, frames, counts, cid, cnt, &n_done,
-                                        acc, oc, nc, na, hi, ncnt, ahead);
-            if (rc)
-                return rc;
-            have_counts = ncnt > 0 && n_done == n_slots;
-        }
-        for (int32_t s = 0; s < n_done; ++s) {
-            if (!proposals) {
-                // the real draws, in order: the member lists are the ones the
-                // guesses were drawn from, so they are the same draws
-                int64_t j = -1;
-                if (ek_draw_at(raw, n_raw, pos, counts[s], &j) || j != js[s])
-                    return ek_fail(EK_ESTATE, "ek_pam_sweep: draw %lld for cluster %d, "
-                                              "guessed %lld", (long long)j, cid + s,
-                                   (long long)js[s]);
-            }
-            accept[cid + s] = acc[s];
-            old_cost[cid + s] = oc[s];
-            new_cost[cid + s] = nc[s];
-            n_amb[cid + s] = na[s];
-            if (acc[s])
-                medoids[cid + s] = frames[s];
-        }
-        cid += n_done;
-        if (cid < hi) {
-            // the window stopped here: this cluster's members changed under an
-            // accepted proposal (or it is empty) -- counted and drawn now
-            int64_t prop = -1;
-            double o = 0.0, nw = 0.0;
-            int64_t amb = 0;
-            if (!proposals) {
-                int64_t m = 0;
-                rc = ek_pam_count_members(c, cid, &m);
-                if (rc)
-                    return rc;
-                if (m <= 0) {
-                    *cid_io = cid;
-                    *status = 2;
-                    return EK_OK;
-                }
-                int64_t j = 0;
-                if (ek_draw_at(raw, n_raw, pos, m, &j)) {
-                    *cid_io = cid;
-                    *status = 1;
-                    return EK_OK;
-                }
-                rc = ek_pam_propose_member(c, cid, j, &prop, &o, &nw, &amb);
-            } else {
-                prop = proposals[cid];
-                rc = ek_pam_propose(c, cid, prop, &o, &nw, &amb);
-            }
-            if (rc)
-                return rc;
-            const int a = nw < o;                               // kmedoids.py:683
-            rc = ek_pam_commit(c, a);
-            if (rc)
-                return rc;
-            accept[cid] = a;
-            old_cost[cid] = o;
-            new_cost[cid] = nw;
-            n_amb[cid] = amb;
-            if (a)
-                medoids[cid] = prop;
-            ++cid;
-        }
     }
     *cid_io = cid;
     return EK_OK;
 }
+
 
 extern "C" int ek_pam_propose_ex(ek_ctx *c, int32_t cid, int64_t frame_index,
                                  int64_t n_members, int32_t win_lo,
@@ -1419,30 +1471,10 @@ extern "C" int ek_pam_propose_ex(ek_ctx *c, int32_t cid, int64_t frame_index,
     if (win_count < 0 || win_count > 32 || (win_count > 0 && !moved_mask))
         return ek_fail(EK_EARG, "ek_pam_propose_ex: bad window");
     EK_HIP(hipSetDevice(c->device));
-    c->cnt_cid = -1;
+    c->cnt.invalidate_one();
     return ek_pam_propose_impl(c, cid, frame_index, n_members, nullptr, old_cost,
                                new_cost, n_ambiguous, win_lo, win_count,
                                win_count > 0 ? moved_mask : nullptr);
-}
-
-static int ek_pam_prefetch_centers_impl(ek_ctx *c, const float *aos_dev,
-                                        const double *G_dev, int32_t count,
-                                        int32_t win_lo, int32_t win_count);
-
-extern "C" int ek_pam_prefetch_centers(ek_ctx *c, const float *aos_dev,
-                                       const double *G_dev, int32_t count)
-{
-    return ek_pam_prefetch_centers_impl(c, aos_dev, G_dev, count, 0, 0);
-}
-
-extern "C" int ek_pam_prefetch_centers_window(ek_ctx *c, const float *aos_dev,
-                                              const double *G_dev, int32_t count,
-                                              int32_t win_lo, int32_t win_count)
-{
-    if (c && (win_lo < 0 || win_count < 0 || win_lo + win_count > c->med_K))
-        return ek_fail(EK_EARG, "ek_pam_prefetch_centers_window: clusters [%d,+%d) "
-                                "outside [0,%d)", win_lo, win_count, c->med_K);
-    return ek_pam_prefetch_centers_impl(c, aos_dev, G_dev, count, win_lo, win_count);
 }
 
 static int ek_pam_prefetch_centers_impl(ek_ctx *c, const float *aos_dev,
@@ -1458,8 +1490,8 @@ static int ek_pam_prefetch_centers_impl(ek_ctx *c, const float *aos_dev,
         return ek_fail(EK_EARG, "ek_pam_prefetch_centers: count=%d outside [0,%d]",
                        count, EK_PAM_GROUP);
     EK_HIP(hipSetDevice(c->device));
-    c->pf_count = 0;
-    c->pf_external = true;
+    c->pf.invalidate();
+    c->pf.external = true;
     if (count == 0)
         return EK_OK;
     int rc = ek_pam_vecs_alloc(c);
@@ -1473,9 +1505,25 @@ static int ek_pam_prefetch_centers_impl(ek_ctx *c, const float *aos_dev,
     if (rc)
         return rc;
     for (int32_t j = 0; j < count; ++j)
-        c->pf_frames[j] = -1;
-    c->pf_count = count;
+        c->pf.frames[j] = -1;
+    c->pf.count = count;
     return EK_OK;
+}
+
+extern "C" int ek_pam_prefetch_centers(ek_ctx *c, const float *aos_dev,
+                                       const double *G_dev, int32_t count)
+{
+    return ek_pam_prefetch_centers_impl(c, aos_dev, G_dev, count, 0, 0);
+}
+
+extern "C" int ek_pam_prefetch_centers_window(ek_ctx *c, const float *aos_dev,
+                                              const double *G_dev, int32_t count,
+                                              int32_t win_lo, int32_t win_count)
+{
+    if (c && (win_lo < 0 || win_count < 0 || win_lo + win_count > c->med_K))
+        return ek_fail(EK_EARG, "ek_pam_prefetch_centers_window: clusters [%d,+%d) "
+                                "outside [0,%d)", win_lo, win_count, c->med_K);
+    return ek_pam_prefetch_centers_impl(c, aos_dev, G_dev, count, win_lo, win_count);
 }
 
 extern "C" int ek_pam_propose_center(ek_ctx *c, int32_t cid, int32_t slot,
@@ -1494,11 +1542,11 @@ extern "C" int ek_pam_propose_center(ek_ctx *c, int32_t cid, int32_t slot,
                        (long long)n_members_local);
     if (win_count < 0 || win_count > 32)
         return ek_fail(EK_EARG, "ek_pam_propose_center: bad window");
-    if (slot >= 0 && (!c->pf_external || slot >= c->pf_count))
+    if (slot >= 0 && (!c->pf.external || slot >= c->pf.count))
         return ek_fail(EK_ESTATE, "ek_pam_propose_center: slot %d was not "
                                   "prefetched", slot);
     EK_HIP(hipSetDevice(c->device));
-    c->cnt_cid = -1;
+    c->cnt.invalidate_one();
     rc = ek_pam_amb_room(c, n_members_local);
     if (rc)
         return rc;
@@ -1506,7 +1554,7 @@ extern "C" int ek_pam_propose_center(ek_ctx *c, int32_t cid, int32_t slot,
     const float *newd;
     if (slot >= 0) {
         newd = c->pam_vecs + (size_t)slot * c->n_pad;
-        ++c->pf_hits;
+        ++c->pf.hits;
     } else {
         ek_launch_record_from_center(center_aos_dev, center_G_dev, c->A, c->rec_tmp,
                                      c->stream);
@@ -1515,12 +1563,12 @@ extern "C" int ek_pam_propose_center(ek_ctx *c, int32_t cid, int32_t slot,
                        c->blockmax, c->hist, c->ctl, c->stream);
         EK_CHECK_LAUNCH();
         newd = c->scratch;
-        ++c->pf_misses;
+        ++c->pf.misses;
     }
     ek_launch_pam_trial(c->tiles, c->G, c->A, c->med_aos, c->med_G, K, cid,
-                        c->pam_restore, -1, nullptr, center_aos_dev, center_G_dev,
+                        c->tab.restore, -1, nullptr, center_aos_dev, center_G_dev,
                         c->amb_count, c->moved, c->stream);
-    c->pam_restore = -1;
+    c->tab.restore = -1;
     rc = ek_pam_tail(c, cid, newd, n_members_local, win_lo, win_count,
                      (EkPamOut *)out_dev);
     if (rc)
@@ -1536,9 +1584,9 @@ extern "C" int ek_pam_prefetch_passes(ek_ctx *c, int64_t *restricted,
     if (!c)
         return ek_fail(EK_EARG, "NULL context");
     if (restricted)
-        *restricted = c->pf_sparse;
+        *restricted = c->pf.restricted;
     if (full)
-        *full = c->pf_full;
+        *full = c->pf.full;
     return EK_OK;
 }
 
@@ -1547,9 +1595,9 @@ extern "C" int ek_pam_sparse_stats(ek_ctx *c, int64_t *windows, int64_t *ended_e
     if (!c)
         return ek_fail(EK_EARG, "NULL context");
     if (windows)
-        *windows = c->sp_windows;
+        *windows = c->sp.windows;
     if (ended_early)
-        *ended_early = c->sp_bailed;
+        *ended_early = c->sp.bailed;
     return EK_OK;
 }
 
@@ -1558,7 +1606,7 @@ extern "C" int ek_pam_ahead_stats(ek_ctx *c, int64_t *slots_taken_over)
     if (!c)
         return ek_fail(EK_EARG, "NULL context");
     if (slots_taken_over)
-        *slots_taken_over = c->sp_ahead;
+        *slots_taken_over = c->sp.ahead;
     return EK_OK;
 }
 
@@ -1567,9 +1615,9 @@ extern "C" int ek_pam_prefetch_stats(ek_ctx *c, int64_t *hits, int64_t *misses)
     if (!c)
         return ek_fail(EK_EARG, "NULL context");
     if (hits)
-        *hits = c->pf_hits;
+        *hits = c->pf.hits;
     if (misses)
-        *misses = c->pf_misses;
+        *misses = c->pf.misses;
     return EK_OK;
 }
 

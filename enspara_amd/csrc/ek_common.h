@@ -6,6 +6,7 @@
 
 #include "../../include/enspara_hip.h"
 #include "ek_track.h"
+#include "ek_pam_limits.h"
 
 #define EK_BLOCK 256          // threads per workgroup of the streaming kernels
 #define EK_WAVE 64
@@ -82,8 +83,6 @@ __host__ __device__ inline bool ek_fine_fits(int nb)
 {
     return 4 * nb <= 8 * EK_RED_THREADS;
 }
-// PAM: proposals per prefetch pass / columns per workgroup of the pairs kernel
-#define EK_PAM_GROUP 8
 // plan of one multi-candidate round (ek_spec.hip); written only by the
 // single-workgroup plan/check kernels, read by the kernels that follow
 struct EkPlan {
@@ -348,13 +347,16 @@ void ek_launch_count_members(const int32_t *assign, int64_t n, int32_t cid,
 void ek_launch_select_member(const int32_t *assign, int64_t n, int32_t cid,
                              const int64_t *scan, int64_t j, int64_t *out,
                              hipStream_t s);
+// (total_host / out_host: mapped host memory that receives the same values -- no copy
+// kernel behind the launch)
 void ek_launch_count_members_multi(const int32_t *assign, int64_t n, int32_t cid0,
                                    int count, int32_t *blockcnt, int64_t *scan,
-                                   int64_t *total, hipStream_t s);
+                                   int64_t *total, hipStream_t s,
+                                   int64_t *total_host = nullptr);
 void ek_launch_select_member_multi(const int32_t *assign, int64_t n, int32_t cid0,
                                    int count, const int64_t *scan,
                                    const int64_t *js_dev, int64_t *out,
-                                   hipStream_t s);
+                                   hipStream_t s, int64_t *out_host = nullptr);
 void ek_launch_pam_classify(const float *dist, const int32_t *assign,
                             const float *newd, int64_t n, int32_t cid,
                             float *ndist, int32_t *nassign, uint32_t *amb,
@@ -411,14 +413,7 @@ struct EkPamOut {
     uint32_t moved;      // bit i: membership of cluster win_lo + i would change
 };
 static_assert(sizeof(EkPamOut) == 32, "EkPamOut layout");
-// a window of proposals decided on the device (ek_pam_window_run): up to
-// EK_PAM_WIN consecutive clusters, their proposals drawn, prefetched (in groups
-// of EK_PAM_GROUP columns) and decided without a host round trip in between
-#ifndef EK_PAM_WIN
-#define EK_PAM_WIN 32     // (16 in round 2: the set-up of a window is ~240 us whatever its width)
-#endif
-static_assert(EK_PAM_WIN % EK_PAM_GROUP == 0 && EK_PAM_WIN <= 32,
-              "whole column groups; the stale mask is 32 bits");
+// the record of a window of proposals decided on the device (ek_pam_limits.h: EK_PAM_WIN)
 struct EkPamWin {
     int32_t stop;       // slots [0, stop) were decided
     uint32_t stale;     // clusters of the window whose membership changed
@@ -519,7 +514,7 @@ void ek_launch_pam_trial(const float *tiles, const double *G, int A, float *aos,
                          hipStream_t s, EkPamWin *win = nullptr, int win_slots = 0);
 // numpy's summation order (ek_pam.hip, "cost sums in numpy's order")
 #define EK_PW_CHUNK 8192            // numpy's reduction buffer, in elements
-#define EK_PW_FULL_LEAVES 64        // leaves of a full chunk (128 elements each)
+// (EK_PW_FULL_LEAVES, the leaves of a full chunk, 128 elements each: ek_pam_limits.h)
 #define EK_PW_MAX_LEAVES 128        // leaves (and internal nodes) of any chunk
 struct EkPwShape {
     int32_t n_leaves, n_nodes, n_levels, pad;

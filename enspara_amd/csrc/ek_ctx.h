@@ -5,6 +5,7 @@
 #pragma once
 #include "ek_common.h"
 #include "ek_pam_sparse.h"
+#include "ek_pam_policy.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -107,6 +108,83 @@ struct EkCopyPool {
     }
 };
 
+// ---- the PAM window path's state (ek_api_pam.hip), a member of the context each --------
+// The buffers stay members of the context itself (ek_free_all); these say what is in them.
+// invalidate(): what they describe no longer holds; begin(): a sweep begins (ek_pam_begin).
+
+// The prefetched distance vectors (pam_vecs): slot j holds the vector of frame
+// frames[j], or of a caller-supplied center.
+struct EkPamPrefetch {
+    int64_t frames[EK_PAM_WIN];
+    int32_t count = 0;
+    bool external = false;          // slots hold caller-supplied centers
+    bool members = false;           // the window's proposals are members of its clusters
+                                    //   (drawn by ek_pam_sweep): tables as bounds
+    EkVecs vecs;                    // where pam_vecs is not +inf (at act_list)
+    EkPrefetchForm form;            // the pauses of the restricted form
+    int64_t hits = 0, misses = 0;   // proposals served from a prefetched vector, not served
+    int64_t restricted = 0, full = 0;   // prefetch passes of either kind
+    void invalidate() { count = 0; }
+    void begin()
+    {
+        invalidate();
+        external = false;
+        form.begin();
+    }
+};
+
+// The window tables (dtab) and the medoid table (med_aos) they were made from.
+struct EkPamTables {
+    int32_t lo = -1, n = 0;         // the window (first cluster, slots) dtab was made for
+    int32_t restore = -1;           // row of the trial table a rejected proposal left
+    void made(int32_t lo_, int32_t n_)
+    {
+        lo = lo_;
+        n = n_;
+    }
+    void invalidate() { n = 0; }    // the medoid table has moved on
+};
+
+// The member counts at hand: of one cluster (scan), of a window's clusters (bat_scan).
+struct EkPamCounts {
+    int32_t cid = -1;               // cluster of the last member count
+    int64_t m = 0;
+    int32_t bat_cid0 = -1, bat_count = 0;
+    void one(int32_t cid_, int64_t m_)
+    {
+        cid = cid_;
+        m = m_;
+    }
+    void batch(int32_t cid0, int32_t count)
+    {
+        bat_cid0 = cid0;
+        bat_count = count;
+    }
+    bool batch_covers(int32_t cid0, int32_t count) const
+    {
+        return bat_cid0 == cid0 && count >= 1 && count <= bat_count;
+    }
+    void invalidate_one() { cid = -1; }
+    // (the scans describe the state at count time only)
+    void invalidate_batch() { batch(-1, 0); }
+};
+
+// The one-workgroup window (ek_pam_sparse.hip).
+struct EkPamOneWg {
+    bool ready = false;             // act_list holds the list of the window just prefetched
+    int64_t n_act = 0;              //   ... this many frames
+    bool bcnt_clean = false;        // the buckets' lengths are zero (the finish kernel's doing)
+    EkSpWait wait;                  // windows to go the three-launch way after one ended early
+    int64_t windows = 0, bailed = 0;
+    int64_t ahead = 0;              // slots whose evaluation ahead was taken over
+    void invalidate() { ready = false; }
+    void begin()
+    {
+        invalidate();
+        wait.begin();
+    }
+};
+
 struct ek_ctx {
     int device = 0;
     int64_t n = 0;
@@ -174,15 +252,13 @@ struct ek_ctx {
     int64_t ambt_cap = 0;
     int32_t med_K = 0, med_cap = 0;
     int32_t pam_cid = -1;            // proposal pending commit
-    int32_t cnt_cid = -1;            // cluster of the last member count
-    int64_t cnt_m = 0;
     int64_t pam_frame = -1;
     // proposal prefetch: member lists of a window of clusters and the distance
     // vectors of up to EK_PAM_WIN proposed frames
     int32_t *bat_blockcnt = nullptr; // [EK_PAM_WIN][nb]
     int64_t *bat_scan = nullptr;     // [EK_PAM_WIN][nb]
     int64_t *bat_sel = nullptr;      // [0..8) counts, [8..16) selected frames
-    int32_t bat_cid0 = -1, bat_count = 0;
+    EkPamCounts cnt;                 // which member counts are at hand
     float *pam_vecs = nullptr;       // [EK_PAM_WIN][n_pad]
     float *pam_dprop = nullptr;      // [EK_PAM_WIN] the proposals' distances to their medoids
     int64_t *sel_host = nullptr;     // pinned [EK_PAM_WIN]: the selected frames on their way back
@@ -190,51 +266,35 @@ struct ek_ctx {
     int64_t *js_host = nullptr;      // pinned [EK_PAM_WIN]: the drawn member ranks on their way in
     int pam_zero_copy = 1;           // kernels write the window's small results into mapped
                                      //   host memory themselves (option key 20)
-    bool pf_members = false;         // the window's proposals are members of its clusters
-                                     //   (drawn by ek_pam_sweep): tables as bounds
-    int pam_bounds = 1;              // use that (option key 16)
-    int pam_bounds_off = 0;          // windows to go with exact tables (the bounds were too loose)
+    int pam_bounds = 1;              // a window of drawn proposals: tables as bounds (option key 16)
     unsigned char *pam_recs = nullptr;
     EkPlan *pam_plan = nullptr;
     unsigned int *moved = nullptr;
-    int64_t pf_frames[EK_PAM_WIN];
-    int32_t pf_count = 0;
-    bool pf_external = false;        // slots hold caller-supplied centers
+    EkPamPrefetch pf;                // what pam_vecs holds, and how it came there
     EkPamOut *pam_out_dev = nullptr; // result record of a proposal
     EkPamOut *pam_out_host = nullptr;    // pinned copy the host polls for
     EkPamWin *pam_win_dev = nullptr;     // a window of proposals decided on the device
     EkPamWin *pam_win_host = nullptr;    // pinned
-    int32_t pam_restore = -1;        // row of the trial table a rejected proposal left
     int32_t *med_list = nullptr;     // [med_cap] medoids within reach (ek_pam_prune_kernel)
     float *dtab = nullptr;           // window tables, three blocks of EK_PAM_WIN * (med_cap + 1):
                                      // T medoid-to-proposal, O medoid-to-old-medoid, dmin
-    int32_t tab_lo = -1, tab_n = 0;  // the window (first cluster, slots) the tables were made for
+    EkPamTables tab;                 // the window they were made for; the trial row to put back
     unsigned int *act_n_host = nullptr;  // pinned
-    int64_t pf_sparse = 0, pf_full = 0;  // prefetch passes of either kind
-    int32_t pf_backoff = 0;          // windows to go before the restricted form is tried again
     int prune = 1;                   // use it (option key 6)
     bool state_exact = true;         // dist[f] IS the distance to medoid assign[f]
     int64_t *tmp_idx = nullptr;      // scratch for index lists
     int64_t tmp_idx_cap = 0;
-    int64_t pf_hits = 0, pf_misses = 0;
     // windows worked through by one workgroup (ek_pam_sparse.hip)
     int pam_sparse = 1;              // use them where they apply (option key 12)
     int64_t sp_max_pairs = EK_SP_MAX_PAIRS;  // (option key 13)
     int sp_exact = 0;                // (option key 14)
-    bool sp_ready = false;           // act_list holds the list of the window just prefetched
+    EkPamOneWg sp;                   // their list, their wait, their statistics
     uint32_t *act_list = nullptr;    // [n] the frames a window's proposals can touch
-    int64_t vecs_rows = -1;          // >= 0: pam_vecs is +inf except at act_list[0 .. vecs_rows)
-    int32_t vecs_cols = 0;           //   of its first vecs_cols vectors
-    int64_t sp_nact = 0;
     unsigned char *sp_buf = nullptr; // the slots' buckets and their lengths
-    int64_t sp_windows = 0, sp_bailed = 0;
     int pam_spec = 1;                // a window's slots evaluated at once, ahead of their turn (option key 19)
     unsigned long long *sp_marks = nullptr;  // [n] which slots' buckets a frame is in and which
                                      //   would change it (zero between windows)
     hipEvent_t win_ev = nullptr;     // a window's record is on the host
-    int64_t sp_ahead = 0;            // slots whose evaluation ahead was taken over
-    bool sp_bcnt_clean = false;      // the buckets' lengths are zero (the finish kernel's doing)
-    int32_t sp_backoff = 0, sp_backoff_next = 8;    // windows to go the three-launch way after one ended early
 
     // multi-candidate rounds (ek_spec.hip)
     int cands = -1;              // candidates per pass: -1 auto, 1 = one-center passes
@@ -362,15 +422,6 @@ void ek_launch_pam_setup_dev(const float *aos, const double *G, int A,
                              unsigned char *recs, float *ctile, double *ctrace,
                              EkPlan *plan, unsigned int *counter, hipStream_t s,
                              const float *dist, float *dprop);
-// (as in ek_common.h, with mapped host memory that receives the same values -- no copy
-// kernel behind the launch)
-void ek_launch_count_members_multi(const int32_t *assign, int64_t n, int32_t cid0,
-                                   int count, int32_t *blockcnt, int64_t *scan,
-                                   int64_t *total, hipStream_t s, int64_t *total_host);
-void ek_launch_select_member_multi(const int32_t *assign, int64_t n, int32_t cid0,
-                                   int count, const int64_t *scan,
-                                   const int64_t *js_dev, int64_t *out,
-                                   hipStream_t s, int64_t *out_host);
 extern int ek_pam_pairs_form;    // ek_pam.hip: the pairs kernels through the matrix cores (key 21)
 int ek_form_slot(int T);
 int ek_spec_alloc(ek_ctx *c);

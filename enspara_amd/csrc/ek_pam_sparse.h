@@ -3,15 +3,7 @@
 #include "ek_common.h"
 
 #define EK_SP_THREADS 512
-// frames on a window's list (ek_pam_active_kernel) up to which the one-workgroup
-// form is used; above it the three launches per proposal of ek_pam.hip are
-#define EK_SP_CAP 65536
-// (ambiguous member, medoid within reach) pairs one workgroup searches itself;
-// a proposal with more ends the window and goes through the launches
-#define EK_SP_MAX_PAIRS 16384
-// chunks of 8192 frames whose sums the workgroup keeps in LDS (shards of up to
-// 8.4 million frames)
-#define EK_SP_MAX_CHUNKS 1024
+// (EK_SP_CAP, EK_SP_MAX_PAIRS, EK_SP_MAX_CHUNKS: ek_pam_limits.h, by way of ek_common.h)
 // frames a proposal may change (a proposal with more ends the window)
 #define EK_SP_CAP_CHG 2048
 

@@ -363,7 +363,10 @@ def test_mailbox_rounds_between_contexts(shards, n, A, K, cutoff, cands):
     (120, 0, {}),
     # (the bench shapes' atom counts, three and more shards: mailboxes of 50 - 800 KB; 7 of
     # these 60 runs went wrong while uncached memory was still handed back to hipFree)
-    (60, 50, {"FUZZ_ATOMS": "300,500", "FUZZ_SHARDS_MIN": "3"})])
+    (60, 50, {"FUZZ_ATOMS": "300,500", "FUZZ_SHARDS_MIN": "3"}),
+    # (frames that are copies of a few distinct ones, laid out against the shard bounds
+    # -- tests/_tied_cases.py: maxima tied within and across shards; n <= 5000.  13 s on the MI355X)
+    (400, 70, {"FUZZ_DATA": "tiled"})])
 def test_mailbox_rounds_in_a_process_that_has_seen_many_contexts(cases, seed, env_extra):
     """tools/fuzz_ms.py: randomized multi-shard runs in ONE process (1 .. 8 shards, ragged
     and empty shards, 1 .. 100 atoms or 300 / 500, center counts and cut-offs, the ladder and pinned round

@@ -648,3 +648,201 @@ def test_kmedoids_across_ranks_without_a_random_state(world):
         np.testing.assert_array_equal(
             d[sel].astype(np.float32),
             qcp.rmsd(x, x[int(g)])[sel].astype(np.float32))
+
+
+# ---- exact ties: copies of one frame within a shard and across shard boundaries --------
+# (tests/_tied_cases.py; synth.synth alone never ties a maximum at a non-zero distance.)
+# The winner is the reference's "lowest rank wins ties" (kcenters.py:337) = the lowest
+# global index; a shard offers the FIRST of its tied frames.
+_TIED_FORMS = [("one", "one", 1, False), ("one_ti", "one", 1, True),
+               ("rounds4", "rounds", 4, False), ("chain8", "chain", 8, False),
+               ("ms8", "ms", 8, False), ("ms16", "ms", 16, False),
+               ("ms32", "ms", 32, False)]
+
+
+def _few_threads():
+    """(the OpenMP runtime is loaded with torch, before a worker can set
+    OMP_NUM_THREADS: several ranks with a thread per core each spend their time
+    spinning -- a hundred times the run time of these small shards)"""
+    from oracle import qcp
+    qcp.set_num_threads(1)
+    torch.set_num_threads(1)
+
+
+def _tied_shard(form, xyz, lo, cands):
+    from _host_shard import (HostShard, HostShardRounds, HostShardChain,
+                             HostShardMs)
+    if form == "one":
+        return HostShard(xyz, lo)
+    return {"rounds": HostShardRounds, "chain": HostShardChain,
+            "ms": HostShardMs}[form](xyz, lo, cands)
+
+
+def _tied_worker(rank, world, port, shape, runs, outdir):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from enspara_amd import sharded
+    import _tied_cases as tc
+    _few_threads()
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port,
+                            rank=rank, world_size=world)
+    n, A, B, w, seed = shape
+    assert w == world
+    x, _ = tc.tied_frames(n, A, B, world, seed)
+    lo, cnt = sharded.shard_bounds(n, world, rank)
+    out = {}
+    for key, K, cutoff in runs:
+        for name, form, cands, ti in _TIED_FORMS:
+            shard = _tied_shard(form, x[lo:lo + cnt], lo, cands)
+            idx, cd = sharded.kcenters_sharded(shard, 0, K if K else n, cutoff,
+                                               check_every=4,
+                                               use_triangle_inequality=ti)
+            tag = "%s_%s_" % (key, name)
+            out[tag + "idx"], out[tag + "cd"] = idx, cd
+            out[tag + "dist"], out[tag + "assign"] = shard.dist, shard.assign
+    np.savez(os.path.join(outdir, "r%d.npz" % rank), **out)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("which", ["MAIN", "TWO_SHARDS", "ONE_EMPTY",
+                                   "EIGHT_SOME_EMPTY"])
+def test_tied_maxima_across_ranks(which):
+    """every form of the sharded loop this file runs (one exchange per center,
+    with and without use_triangle_inequality; rounds; chained rounds; one
+    exchange per round at 8 / 16 / 32 candidates) on frames whose maxima are
+    tied across the shard boundaries: K centers, more centers than there are
+    distinct frames, and a cut-off that IS a tied maximum (strict >: every rank
+    stops exactly there).  Worlds 2 and 3, 3 with an empty shard, 8 with two."""
+    from oracle import cluster as oc
+    import _tied_cases as tc
+    shape = getattr(tc, which)
+    n, A, B, world, seed = shape
+    K = {"MAIN": tc.MAIN_K, "TWO_SHARDS": tc.TWO_SHARDS_K,
+         "ONE_EMPTY": tc.ONE_EMPTY_K, "EIGHT_SOME_EMPTY": tc.EIGHT_K}[which]
+    x, ids = tc.tied_frames(n, A, B, world, seed)
+    cutoff, k_cut = tc.tied_cutoff(x, K, world)
+    K_more = B + B // 3                     # (MAIN: 80)
+    runs = [("count", K, 0.0), ("more", K_more, 0.0), ("cut", None, cutoff)]
+    with tempfile.TemporaryDirectory() as d:
+        mp.spawn(_tied_worker, args=(world, _free_port(), shape, runs, d),
+                 nprocs=world, join=True)
+        parts = [np.load(os.path.join(d, "r%d.npz" % r)) for r in range(world)]
+    for key, Kr, cut in runs:
+        inds, a, dd = oc.kcenters(x, n_clusters=Kr, dist_cutoff=cut or None)
+        assert len(inds) == (Kr if Kr else k_cut)
+        if key == "more":
+            assert len(set(ids[[int(i) for i in inds]].tolist())) == B
+        if key == "cut":
+            assert dd.max() == cut
+        for name, _, _, _ in _TIED_FORMS:
+            tag = "%s_%s_" % (key, name)
+            for p in parts:
+                np.testing.assert_array_equal(p[tag + "idx"], np.array(inds), tag)
+            np.testing.assert_array_equal(
+                np.concatenate([p[tag + "assign"] for p in parts]), a, tag)
+            np.testing.assert_array_equal(
+                np.concatenate([p[tag + "dist"] for p in parts]).astype(np.float64),
+                dd, tag)
+
+
+def _tied_init_centers(x, ids, n, world):
+    """initial centers that are copies of one another and of store frames: a late
+    copy of a frame that occurs in every shard (its label's closest members are
+    tied at the same distance in all shards: the first in the global order is in
+    shard 0), the same frame again (attracts nothing), the frame whose first copy
+    is the last frame of shard 0 by a later copy, the one whose first copy opens
+    shard 1, and one of the last tile's"""
+    import _tied_cases as tc
+    sp = tc.specials(n, int(ids.max()) + 1, world)
+    every = np.flatnonzero(ids == 3)
+    return [x[every[-1]], x[every[len(every) // 2]],
+            x[np.flatnonzero(ids == sp["last_id"])[-1]],
+            x[np.flatnonzero(ids == sp["first_id"])[-1]],
+            x[sp["tail_pos"][-1]]]
+
+
+def _tied_warm_worker(rank, world, port, shape, K, pam_seed, outdir):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from enspara_amd import sharded
+    import _tied_cases as tc
+    _few_threads()
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port,
+                            rank=rank, world_size=world)
+    n, A, B, _, seed = shape
+    x, ids = tc.tied_frames(n, A, B, world, seed)
+    init = _tied_init_centers(x, ids, n, world)
+    lo, cnt = sharded.shard_bounds(n, world, rank)
+    out = {}
+    for name, form, cands in (("one", "one", 1), ("ms16", "ms", 16)):
+        shard = _tied_shard(form, x[lo:lo + cnt], lo, cands)
+        ctr = sharded.warm_start_sharded(shard, init)
+        idx, cd = sharded.kcenters_sharded(shard, len(ctr), K - len(ctr), 0.0,
+                                           check_every=4)
+        out[name + "_ctr"] = np.array(ctr)
+        out[name + "_idx"] = np.array(ctr + [int(i) for i in idx])
+        out[name + "_dist"], out[name + "_assign"] = shard.dist, shard.assign
+    # k-hybrid, two sweeps: the proposals are drawn among members that are copies
+    for name, form, cands in (("hy_one", "one", 1), ("hy_rounds", "rounds", 4)):
+        shard = _tied_shard(form, x[lo:lo + cnt], lo, cands)
+        med = sharded.khybrid_sharded(shard, K, 0.0, 2, random_state=pam_seed)
+        out[name + "_idx"] = np.array(med)
+        out[name + "_dist"], out[name + "_assign"] = shard.dist, shard.assign
+    np.savez(os.path.join(outdir, "r%d.npz" % rank), **out)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("which", ["MAIN", "TWO_SHARDS"])
+def test_tied_warm_start_and_khybrid_across_ranks(which):
+    """warm_start_sharded with duplicate initial centers that are copies of store
+    frames: the closest members of a label are tied across the shards and
+    _closest_members must name the lowest global index; then the loop continues.
+    And one k-hybrid run with two sweeps on the same frames, with a random
+    stream under which no proposal's verdict hangs on the order of the cost's
+    float64 sum (tc.pam_cost_ties).  (It does for TWO_SHARDS with seeds 5 and 6:
+    the second sweep's proposal for cluster 8 leaves a permutation of the
+    squared distances, the whole-array mean finds the costs equal, the sum of
+    the two shards' sums finds 0.5074568650390516 < 0.5074568650390517 and moves
+    the medoid from 518 to 936.)"""
+    from oracle import cluster as oc
+    import _tied_cases as tc
+    shape = getattr(tc, which)
+    n, A, B, world, seed = shape
+    K = tc.MAIN_K if which == "MAIN" else tc.TWO_SHARDS_K
+    pam_seed = 5 if which == "MAIN" else 7
+    x, ids = tc.tied_frames(n, A, B, world, seed)
+    assert tc.pam_cost_ties(x, K, world, pam_seed, 2) == []
+    with tempfile.TemporaryDirectory() as d:
+        mp.spawn(_tied_warm_worker, args=(world, _free_port(), shape, K, pam_seed, d),
+                 nprocs=world, join=True)
+        parts = [np.load(os.path.join(d, "r%d.npz" % r)) for r in range(world)]
+    init = _tied_init_centers(x, ids, n, world)
+    inds, a, dd = oc.kcenters(x, n_clusters=K, init_centers=init)
+    assert len(inds) == K
+    # four occupied labels, each represented by the FIRST copy of its frame; three
+    # of those lie in an earlier shard than the copy that was passed in
+    sp = tc.specials(n, B, world)
+    want_ctr = [int(np.flatnonzero(ids == 3)[0]), sp["last_pos"], sp["first_pos"],
+                int(sp["tail_pos"][0])]
+    assert [int(i) for i in inds[:4]] == want_ctr
+    hi, ha, hd = oc.kcenters(x, n_clusters=K)
+    rs = np.random.RandomState(pam_seed)
+    moved = 0
+    for _ in range(2):
+        ni, hd, ha = oc.pam_update(x, hi, ha, hd, random_state=rs)
+        moved += sum(int(p) != int(q) for p, q in zip(ni, hi))
+        hi = ni
+    assert moved > 0
+    for name, wi, wa, wd in (("one", inds, a, dd), ("ms16", inds, a, dd),
+                             ("hy_one", hi, ha, hd), ("hy_rounds", hi, ha, hd)):
+        for p in parts:
+            np.testing.assert_array_equal(p[name + "_idx"], np.array(wi), name)
+            if name + "_ctr" in p:
+                assert [int(i) for i in p[name + "_ctr"]] == want_ctr
+        np.testing.assert_array_equal(
+            np.concatenate([p[name + "_assign"] for p in parts]), wa, name)
+        np.testing.assert_array_equal(
+            np.concatenate([p[name + "_dist"] for p in parts]).astype(np.float64),
+            wd, name)

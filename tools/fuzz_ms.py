@@ -1,11 +1,15 @@
 """Scratch: randomized comparison with the oracle, part 4: the rounds ACROSS shards with the
 exchange on the device (csrc/ek_mshard.hip, ek_ms_run) -- the shards are contexts of this one
 process on the one GPU, mailboxes by address, every shard's loop in its own host thread.
-Random shard counts (ragged and empty shards), frame / atom / template counts (duplicates and
-ties when the templates are few), center counts or distance cut-offs, round widths (the
-ladder, 8, 16, 32), the per-prefix maxima in the pass or in the chain kernel, and the exchange
+Random shard counts (ragged and empty shards), frame / atom / template counts, center counts or
+distance cut-offs, round widths (the ladder, 8, 16, 32), the per-prefix maxima in the pass or in the chain kernel, and the exchange
 in two steps (per-prefix maxima first) or in one.  Every center, label and distance against
-oracle.cluster.kcenters.  usage: fuzz_ms.py [n_cases] [seed] [first_case]; FUZZ_VERBOSE=1
+oracle.cluster.kcenters.  The frames are synth.synth's: every frame has its own noise and
+rotation, so no two are equal and no maximum is tied at a non-zero distance, however few the
+templates (the only ties are the all-zero ones of one atom).  FUZZ_DATA=tiled draws the case's
+frames with tests/_tied_cases.py tied_frames instead -- copies of a few distinct frames laid
+out against the shard bounds, maxima tied within and across shards -- with n capped at 5000.
+usage: fuzz_ms.py [n_cases] [seed] [first_case]; FUZZ_VERBOSE=1
 prints every case before it runs."""
 import os
 import sys
@@ -19,6 +23,10 @@ import numpy as np
 from enspara_amd import sharded, synth
 from enspara_amd.device import FrameStore
 from oracle import cluster as oc
+if os.environ.get("FUZZ_DATA") == "tiled":
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                    "tests"))
+    from _tied_cases import tied_frames
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 base = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -49,13 +57,24 @@ for case in range(first, first + cases):
         shards = max(shards, int(os.environ["FUZZ_SHARDS_MIN"]))
     if os.environ.get("FUZZ_SWEEP"):
         sweep = int(os.environ["FUZZ_SWEEP"])
-    x = synth.synth(n, A, nt, seed=int(rng.randint(1 << 30)))
+    if os.environ.get("FUZZ_DATA") == "tiled":  # (nothing more is drawn from rng: the cases' sequence stays)
+        n = min(n, 5000)
+        nd = max(9, min(n // 4, 3 * nt + 9))
+        xseed = int(rng.randint(1 << 30))
+        try:
+            x, _ = tied_frames(n, A, nd, shards, xseed)
+        except ValueError:      # (a last shard of a few frames: plain copies in turn)
+            x = synth.synth(9, A, 3, seed=xseed)[np.arange(n) % 9]
+    else:
+        x = synth.synth(n, A, nt, seed=int(rng.randint(1 << 30)))
     if rng.randint(4) == 0:
         K, cutoff = 0, float(rng.choice([0.2, 0.5, 1.0]))
     else:
         K, cutoff = int(min(n, rng.choice([1, 2, 17, 64, 200, 700]))), 0.0
     tag = "case %d shards=%d n=%d A=%d nt=%d K=%d cutoff=%g cands=%d two=%d sweep=%d" % (
         case, shards, n, A, nt, K, cutoff, cands, two, sweep)
+    if os.environ.get("FUZZ_DATA"):
+        tag += " data=" + os.environ["FUZZ_DATA"]
     if os.environ.get("FUZZ_VERBOSE"):
         print(tag, flush=True)
     if os.environ.get("FUZZ_MEM"):      # (free device memory before the case: a leak shows)

@@ -27,22 +27,24 @@ distance, global index, that sample's features), one launch per center and
 rank (csrc/ek_feat_kcenters.hip ``feat_shard_step_kernel``) -- and
 :func:`fit_features_sharded` is the estimators' ``mpi_mode`` for them: same
 centers, labels and float64 distances as the single-process loop.  No rounds
-of several candidates, no mailbox transport and no sharded PAM there.
+of several candidates and no mailbox transport there; the PAM sweeps
+(:func:`pam_sweep_sharded`) run over either kind of shard.
 """
+import collections
+import contextlib
+
 import numpy as np
 
 
-class DeviceShard:
-    """Shard protocol on top of a :class:`enspara_amd.device.FrameStore`.
-
-    Records live in torch CUDA tensors so that torch.distributed can move
-    them.  The FrameStore must have been created on a non-default torch
-    stream (``s = torch.cuda.Stream(); FrameStore(..., stream=s.cuda_stream)``)
-    and the driver must run under ``with torch.cuda.stream(s)``: torch orders
-    its collectives against the current stream, so kernels and the all-gather
-    are then ordered on the device without host syncs.  (Handle 0, the legacy
-    default stream, means "create your own" to ek_ctx_create.)
-    """
+class _StoreShard:
+    """What :class:`DeviceShard` and :class:`FeatureShard` share: the store's
+    records and state in torch CUDA tensors that torch.distributed can move.
+    The store must have been created on a non-default torch stream (``s =
+    torch.cuda.Stream()``, handed over as ``stream=s.cuda_stream``) and the
+    driver must run under ``with torch.cuda.stream(s)``: torch orders its
+    collectives against the current stream, so kernels and the all-gather are
+    then ordered on the device without host syncs.  (Handle 0, the legacy
+    default stream, means "create your own" to ek_ctx_create.)"""
 
     def __init__(self, store):
         import torch
@@ -54,12 +56,71 @@ class DeviceShard:
     def record_bytes(self):
         return self.store.record_bytes
 
+    @property
+    def n_local(self):
+        return self.store.n
+
+    @property
+    def offset(self):
+        return self.store.global_offset
+
     def new_buffer(self, nbytes):
         return self.torch.empty(nbytes, dtype=self.torch.uint8,
                                 device=self.device)
 
     def local_candidate(self, rec):
         self.store.local_candidate(rec.data_ptr())
+
+    def progress(self):
+        """-> number of centers so far; synchronises"""
+        _, _, n_done = self.store.history(0, 0)
+        return n_done
+
+    def history(self, first, count):
+        return self.store.history(first, count)
+
+    def reset_history(self):
+        self.store.reset_history()
+
+    def state(self):
+        """-> (distances [n_local], labels int32 [n_local]) on the host"""
+        return self.store.download_state()
+
+    def set_state(self, distances, assignments):
+        """the caller's per-frame state (a warm start, kmedoids.py:133-146)"""
+        self.store.upload_state(distances, assignments)
+
+    def host_to_buffer(self, arr):
+        """int64 numpy array -> tensor a collective can move"""
+        return self.torch.from_numpy(np.ascontiguousarray(
+            arr, dtype=np.int64)).to(self.device)
+
+    def to_host(self, t):
+        """Small device tensor -> numpy, waiting by polling an event: a
+        blocking synchronize can cost far more than the proposal it guards
+        when the host thread is put to sleep."""
+        torch = self.torch
+        h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        h.copy_(t, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        while not ev.query():
+            pass
+        return h.numpy()
+
+    def pam_count_batch(self, cid0, count):
+        return self.store.pam_count_members_batch(cid0, count)
+
+    def pam_select_batch(self, cid0, js):
+        return self.store.pam_select_members_batch(cid0, js)
+
+    def pam_commit(self, accept):
+        self.store.pam_commit(accept)
+
+
+class DeviceShard(_StoreShard):
+    """Shard protocol on top of a :class:`enspara_amd.device.FrameStore`
+    (float32 distances; stream rules: :class:`_StoreShard`)."""
 
     def step(self, all_recs, n_recs, label, cutoff, own_rec):
         self.store.kcenters_step(all_recs.data_ptr(), n_recs, label, cutoff,
@@ -89,23 +150,10 @@ class DeviceShard:
         the state becomes (nearest center, distance), util.py:199-203"""
         self.store.assign_nearest(centers_xyz)
 
-    def state(self):
-        """-> (distances float32 [n_local], labels int32 [n_local]) on the host"""
-        return self.store.download_state()
-
-    def set_state(self, distances, assignments):
-        """the caller's per-frame state (a warm start, kmedoids.py:133-146)"""
-        self.store.upload_state(distances, assignments)
-
     def set_exact(self, on):
         """every frame's distance IS the one to the medoid its label names
         (option key 7: lets the PAM search use the triangle inequality)"""
         self.store.set_option("state_exact", 1 if on else 0)
-
-    def progress(self):
-        """-> number of centers so far; synchronises"""
-        _, _, n_done = self.store.history(0, 0)
-        return n_done
 
     # multi-candidate rounds
     @property
@@ -166,43 +214,10 @@ class DeviceShard:
         idx, cd, _ = self.store.ms_run(first_label, max_new, cutoff)
         return idx, cd
 
-    def history(self, first, count):
-        idx, cd, n_done = self.store.history(first, count)
-        return idx, cd, n_done
-
-    def reset_history(self):
-        self.store.reset_history()
-
     # PAM across shards: centers travel as centred coordinates + trace
     @property
     def n_atoms(self):
         return self.store.A
-
-    @property
-    def n_local(self):
-        return self.store.n
-
-    @property
-    def offset(self):
-        return self.store.global_offset
-
-    def host_to_buffer(self, arr):
-        """int64 numpy array -> tensor a collective can move"""
-        return self.torch.from_numpy(np.ascontiguousarray(
-            arr, dtype=np.int64)).to(self.device)
-
-    def to_host(self, t):
-        """Small device tensor -> numpy, waiting by polling an event: a
-        blocking synchronize can cost far more than the proposal it guards
-        when the host thread is put to sleep."""
-        torch = self.torch
-        h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-        h.copy_(t, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        while not ev.query():
-            pass
-        return h.numpy()
 
     def new_table(self, rows):
         """-> (coords float32 [rows, 3A], meta int64 [2 * rows]), zeroed;
@@ -222,12 +237,6 @@ class DeviceShard:
         self.store.pam_begin_table(coords.data_ptr(), meta.data_ptr(),
                                    n_medoids)
 
-    def pam_count_batch(self, cid0, count):
-        return self.store.pam_count_members_batch(cid0, count)
-
-    def pam_select_batch(self, cid0, js):
-        return self.store.pam_select_members_batch(cid0, js)
-
     def pam_count(self, cid):
         return self.store.pam_count_members(cid)
 
@@ -245,60 +254,22 @@ class DeviceShard:
             meta.data_ptr() + 8 * row, n_members_local, win_lo, win_count,
             out.data_ptr())
 
-    def pam_commit(self, accept):
-        self.store.pam_commit(accept)
 
-
-class FeatureShard:
+class FeatureShard(_StoreShard):
     """The one-record shard protocol (``record_bytes``, ``new_buffer``,
     ``local_candidate``, ``step``, ``progress``, ``history``,
     ``reset_history``) on top of a
     :class:`enspara_amd.geometry.libdist.FeatureStore` for ``metric`` 0
-    euclidean / 1 manhattan / 2 hamming.  As with :class:`DeviceShard` the
-    store lives on a non-default torch stream and the driver runs under
-    ``with torch.cuda.stream(s)``.  No ``candidates``: one center per
-    exchange."""
+    euclidean / 1 manhattan / 2 hamming (float64 distances; stream rules:
+    :class:`_StoreShard`).  No ``candidates``: one center per exchange."""
 
     def __init__(self, store, metric):
-        import torch
-        self.torch = torch
-        self.store = store
+        super().__init__(store)
         self.metric = int(metric)
-        self.device = torch.device("cuda", store.device)
-
-    @property
-    def record_bytes(self):
-        return self.store.record_bytes
-
-    @property
-    def n_local(self):
-        return self.store.n
-
-    @property
-    def offset(self):
-        return self.store.global_offset
-
-    def new_buffer(self, nbytes):
-        return self.torch.empty(nbytes, dtype=self.torch.uint8,
-                                device=self.device)
-
-    def local_candidate(self, rec):
-        self.store.local_candidate(rec.data_ptr())
 
     def step(self, all_recs, n_recs, label, cutoff, own_rec):
         self.store.kcenters_step(self.metric, all_recs.data_ptr(), n_recs,
                                  label, cutoff, own_rec.data_ptr())
-
-    def progress(self):
-        """-> number of centers so far; synchronises"""
-        _, _, n_done = self.store.history(0, 0)
-        return n_done
-
-    def history(self, first, count):
-        return self.store.history(first, count)
-
-    def reset_history(self):
-        self.store.reset_history()
 
     def distance(self, y):
         """metric(X_local, y) -> float64 [n_local] on the host (warm start)"""
@@ -316,19 +287,9 @@ class FeatureShard:
         """distances +inf, labels -1"""
         self.store.reset_state()
 
-    def state(self):
-        """-> (distances float64 [n_local], labels int32 [n_local])"""
-        return self.store.download_state()
-
-    def set_state(self, distances, assignments):
-        self.store.upload_state(distances, assignments)
-
     # PAM across shards, the methods pam_sweep_sharded drives (DeviceShard's):
     # rows travel as [rows, n_features] tables in the samples' element kind,
     # the int64 `meta` vector only carries the proposals' global indices
-    host_to_buffer = DeviceShard.host_to_buffer
-    to_host = DeviceShard.to_host
-
     def new_table(self, rows):
         t = self.torch
         dt = {"float32": t.float32, "float64": t.float64,
@@ -342,12 +303,6 @@ class FeatureShard:
 
     def pam_begin_table(self, table, meta, n_medoids):
         self.store.pam_begin(self.metric, table.data_ptr(), n_medoids)
-
-    def pam_count_batch(self, cid0, count):
-        return self.store.pam_count_members_batch(cid0, count)
-
-    def pam_select_batch(self, cid0, js):
-        return self.store.pam_select_members_batch(cid0, js)
 
     def pam_count(self, cid):
         return self.store.pam_count_members_batch(cid, 1)[0]
@@ -364,9 +319,6 @@ class FeatureShard:
             cid, table.data_ptr() + row * table.stride(0) * table.element_size(),
             win_lo, win_count, out.data_ptr())
 
-    def pam_commit(self, accept):
-        self.store.pam_commit(accept)
-
 
 def _to_host(shard, t):
     f = getattr(shard, "to_host", None)
@@ -378,6 +330,18 @@ def _world(group):
     if dist.is_available() and dist.is_initialized():
         return dist.get_world_size(group), dist.get_rank(group)
     return 1, 0
+
+
+def _everyone(mine, group=None):
+    """Every rank's (picklable) ``mine`` in rank order; ``[mine]`` where there
+    is nobody else to ask: one rank, or no process group at all."""
+    import torch.distributed as dist
+    world, _ = _world(group)
+    if world == 1:
+        return [mine]
+    said = [None] * world
+    dist.all_gather_object(said, mine, group=group)
+    return said
 
 
 def kcenters_sharded(shard, first_label, max_new, dist_cutoff=0.0, group=None,
@@ -692,9 +656,6 @@ def _closest_members(d, a, offset, K0, group=None):
     """Per occupied label of 0..K0-1 the member closest to its center, the
     first such member in the GLOBAL order, from every rank's local (distances,
     labels): -> global indices in label order (see ``warm_start_sharded``)."""
-    import torch.distributed as dist
-    world, rank = _world(group)
-    collective = dist.is_available() and dist.is_initialized()
     d = np.asarray(d, dtype=np.float64)
     a = np.asarray(a, dtype=np.int64)
     best_d = np.full(K0, np.inf, dtype=np.float64)
@@ -706,10 +667,7 @@ def _closest_members(d, a, offset, K0, group=None):
         first = np.flatnonzero(np.r_[True, lab[1:] != lab[:-1]])
         best_d[lab[first]] = d[order[first]]
         best_g[lab[first]] = offset + order[first]
-    tables = [(best_d, best_g)]
-    if collective and world > 1:
-        tables = [None] * world
-        dist.all_gather_object(tables, (best_d, best_g), group=group)
+    tables = _everyone((best_d, best_g), group)
     ctr = []
     for lab in range(K0):
         win_d, win_g = np.inf, -1
@@ -929,29 +887,188 @@ def pam_sweep_sharded(shard, medoids, proposals=None, random_state=None,
     return medoids
 
 
+# ---------------------------------------------------------------------------
+# what the estimator-level entries below share: who holds what, agreement
+# before anything can hang, the centers' rows from the ranks that hold them
+# ---------------------------------------------------------------------------
+def _split_indices(starts, indices):
+    """Flat indices into blocks laid end to end (``starts`` [n_blocks + 1]) ->
+    (block, index within it) pairs.  An index on a boundary belongs to the
+    block that holds it, never to an empty block before it."""
+    out = []
+    for g in indices:
+        b = int(np.searchsorted(starts, g, side="right") - 1)
+        out.append((b, int(g) - int(starts[b])))
+    return out
+
+
+class _Layout:
+    """Where every rank's frames / samples lie in the global order (rank r's
+    follow rank r-1's), from every rank's count: ``world``, ``rank``,
+    ``starts`` int64 [world + 1], ``n_total`` and this rank's [``lo``, ``hi``).
+    Without a process group: one rank that holds everything."""
+
+    def __init__(self, counts, group=None):
+        self.group = group
+        self.world, self.rank = _world(group)
+        self.starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.n_total = int(self.starts[-1])
+        self.lo = int(self.starts[self.rank])
+        self.hi = int(self.starts[self.rank + 1])
+
+    @classmethod
+    def gather(cls, n_local, group=None):
+        """collective: every rank says how many it holds"""
+        return cls(_everyone(int(n_local), group), group)
+
+    def pairs(self, global_indices):
+        """-> (rank, local index) pairs, the reference's form of a center
+        index in MPI mode (kcenters.py:375-376)"""
+        return _split_indices(self.starts, global_indices)
+
+
+def _rows_from_owners(which, local, lay):
+    """``local[g - lay.lo]`` for every global index g of ``which``, from the
+    rank that holds it: -> the rows in the order of ``which`` (copies, in the
+    dtype of ``local``), the same list on every rank.  Collective."""
+    mine = {k: local[g - lay.lo].copy() for k, g in enumerate(which)
+            if lay.lo <= g < lay.hi}
+    rows = {}
+    for part in _everyone(mine, lay.group):
+        rows.update(part)
+    return [rows[k] for k in range(len(which))]
+
+
+def _need_group(what="mpi_mode"):
+    import torch.distributed as dist
+    from .exception import ImproperlyConfigured
+    if not (dist.is_available() and dist.is_initialized()):
+        raise ImproperlyConfigured(
+            "%s needs an initialised torch.distributed process group "
+            "(one process per GPU, e.g. under torchrun)" % what)
+
+
+def _agree_on_seed(random_state, group=None):
+    """The sweeps draw member ranks from ONE stream that every rank replays
+    (the reference agrees on each draw, mpi/ops.py randind): ranks that pass
+    different seeds or differently positioned RandomStates would propose
+    different samples and wait for each other forever, so they compare first
+    and raise ImproperlyConfigured together.  None everywhere (also the global
+    numpy RandomState, what the estimators make of None): rank 0's draw for
+    all.  Without a process group there is nobody to agree with.
+    -> RandomState; for an int seed or identically seeded RandomStates exactly
+    ``check_random_state(random_state)``"""
+    import hashlib
+    import torch.distributed as dist
+    from .cluster.kcenters import check_random_state
+    from .exception import ImproperlyConfigured
+    if not (dist.is_available() and dist.is_initialized()):
+        return check_random_state(random_state)
+    if random_state is None or random_state is np.random.mtrand._rand:
+        mark = None
+    elif isinstance(random_state, (int, np.integer)):
+        mark = ("seed", int(random_state))
+    elif isinstance(random_state, np.random.RandomState):
+        st = random_state.get_state()
+        mark = ("state", hashlib.sha1(np.asarray(st[1]).tobytes()).hexdigest(),
+                int(st[2]))
+    else:
+        mark = ("other", repr(random_state))
+    draw = int(np.random.SeedSequence().entropy % (2 ** 31 - 1))
+    everyone = _everyone((mark, draw), group)
+    if len(set(m for m, _ in everyone)) != 1:
+        raise ImproperlyConfigured(
+            "the ranks disagree on random_state (%s): the sharded PAM sweep "
+            "needs the same seed, or identically seeded RandomStates, on "
+            "every rank" % ", ".join(
+                "rank %d: %s" % (r, "None" if m is None else m[0] + " " +
+                                 str(m[1])[:12]) for r, (m, _) in
+                enumerate(everyone)))
+    if mark is None:
+        return check_random_state(everyone[0][1])
+    return check_random_state(random_state)
+
+
+def _raise_together(err, agree, what, group=None):
+    """A rank raising alone would leave the others waiting in the next
+    collective, so every check of a rank's own arguments ends here: ``err`` is
+    None or this rank's (exception class, message), ``agree`` what all ranks
+    must have in common (``what`` names its fields).  If any rank has an error
+    EVERY rank raises the first one's class with all the messages; if they
+    disagree every rank raises ImproperlyConfigured.  Without a process group
+    the exception is the local one, as it is."""
+    from .exception import ImproperlyConfigured
+    world, _ = _world(group)
+    said = _everyone((err, agree), group)
+    bad = [(r, e) for r, (e, _) in enumerate(said) if e is not None]
+    if bad and world == 1:
+        raise err[0](err[1])
+    if bad:
+        raise bad[0][1][0]("; ".join(
+            m if m.startswith("rank ") else "rank %d: %s" % (r, m)
+            for r, (_, m) in bad))
+    if len(set(a for _, a in said)) != 1:
+        raise ImproperlyConfigured(
+            "the ranks disagree on %s: %s" % (what, ", ".join(
+                "rank %d: %s" % (r, a) for r, (_, a) in enumerate(said))))
+
+
+def _cluster_result(shard, pairs, centers):
+    """the ClusterResult of the reference's MPI mode: ``center_indices`` as
+    (rank, local index) pairs, this rank's labels (int64) and distances
+    (float64) from the shard, the centers' rows, the same on every rank"""
+    from .cluster import util
+    d, a = shard.state()
+    return util.ClusterResult(
+        center_indices=pairs, assignments=np.asarray(a).astype(np.int64),
+        distances=np.asarray(d, dtype=np.float64), centers=centers)
+
+
+def _kcenters_then_pam(shard, med, max_new, dist_cutoff, n_iters, rs, group,
+                       use_triangle_inequality=False):
+    """Up to ``max_new`` k-centers iterations after the centers ``med`` already
+    there (a warm start's, or none), then ``n_iters`` PAM sweeps drawing from
+    the RandomState ``rs``, over all ranks' shards (reference hybrid.py:112-162
+    in MPI mode).  -> (the medoids' global indices, how many k-centers added);
+    labels and distances stay on the shards."""
+    idx, _ = kcenters_sharded(shard, len(med), max_new,
+                              float(dist_cutoff or 0.0), group=group,
+                              use_triangle_inequality=use_triangle_inequality)
+    med = list(med) + [int(g) for g in idx]
+    for _ in range(int(n_iters)):
+        med = pam_sweep_sharded(shard, med, random_state=rs, group=group)
+    return med, len(idx)
+
+
+def _fit_on_shard(shard, local, lay, med, max_new, dist_cutoff, n_iters, rs,
+                  init_centers=(), use_triangle_inequality=False):
+    """:func:`_kcenters_then_pam` and its :func:`_cluster_result`: ``centers``
+    = the rows of ``local`` the centers are, from the ranks that hold them.
+    k-centers alone (no sweep) returns ``init_centers``, the warm start's
+    centers as the caller gave them, followed by the new ones."""
+    med, n_new = _kcenters_then_pam(shard, med, max_new, dist_cutoff, n_iters,
+                                    rs, lay.group, use_triangle_inequality)
+    if int(n_iters) > 0:                # every center is a medoid of the data
+        init_centers, n_new = (), len(med)
+    return _cluster_result(
+        shard, lay.pairs(med), list(init_centers) +
+        _rows_from_owners(med[len(med) - n_new:], local, lay))
+
+
 def khybrid_sharded(shard, n_clusters, dist_cutoff=0.0, n_iters=5,
                     random_state=None, group=None):
-    """k-centers then ``n_iters`` PAM sweeps over all ranks' shards (reference
-    hybrid.py:112-162 in MPI mode).  ``random_state`` is wrapped once, so an
-    int seed gives one stream across the sweeps -- what the KHybrid estimator
-    does (hybrid.py:78,103).  Returns the medoids' global frame indices;
+    """k-centers then ``n_iters`` PAM sweeps over all ranks' ready shards
+    (:func:`_kcenters_then_pam`).  ``random_state`` is wrapped once, so an int
+    seed gives one stream across the sweeps -- what the KHybrid estimator does
+    (hybrid.py:78,103) -- and has to be the same on every rank
+    (:func:`_agree_on_seed`).  Returns the medoids' global frame indices;
     labels and distances stay on the shards."""
-    from .cluster.kcenters import check_random_state
-    import torch.distributed as dist
-    rs = check_random_state(random_state)
+    rs = _agree_on_seed(random_state, group)
     if n_clusters is None or np.isinf(n_clusters):
         # cut-off only: same cap as the single-GPU path (cluster/kcenters.py)
-        world, _ = _world(group)
-        lay = _gather_i64(shard, [shard.n_local], group, world,
-                          dist.is_available() and dist.is_initialized())
-        n_clusters = 2 * int(lay.sum()) + 16
-    idx, _ = kcenters_sharded(shard, 0, int(n_clusters), dist_cutoff,
-                              group=group)
-    medoids = [int(i) for i in idx]
-    for _ in range(int(n_iters)):
-        medoids = pam_sweep_sharded(shard, medoids, random_state=rs,
-                                    group=group)
-    return medoids
+        n_clusters = 2 * _Layout.gather(shard.n_local, group).n_total + 16
+    return _kcenters_then_pam(shard, [], int(n_clusters), dist_cutoff, n_iters,
+                              rs, group)[0]
 
 
 # ---------------------------------------------------------------------------
@@ -973,14 +1090,11 @@ def ctr_ids_mpi(cluster_center_inds, lengths, world):
     pairs = cluster_center_inds
     if not hasattr(cluster_center_inds[0], "__len__"):
         # [global frame index, ...] -> [[global trajectory, frame], ...]
-        pairs = []
         for c in cluster_center_inds:
-            c = int(c)
-            if c < 0 or c >= starts[-1]:
+            if int(c) < 0 or int(c) >= starts[-1]:
                 raise IndexError("cluster center index %d outside the %d frames "
                                  "X_lengths describes" % (c, int(starts[-1])))
-            t = int(np.searchsorted(starts, c, side="right") - 1)
-            pairs.append((t, c - int(starts[t])))
+        pairs = _split_indices(starts, [int(c) for c in cluster_center_inds])
     out = []
     for t, f in pairs:
         t, f = int(t), int(f)
@@ -992,285 +1106,253 @@ def ctr_ids_mpi(cluster_center_inds, lengths, world):
     return out
 
 
-def _gather_rows_f32(shard, K, width, rows, values, group, collective):
-    """A float32 table [K, width] of which this rank knows ``rows`` (their
-    ``values``): every row is filled by exactly one rank, the integer sum of
-    the bit patterns over ranks reproduces it everywhere (cf. _share_rows)."""
-    import torch
-    import torch.distributed as dist
-    like = shard.new_buffer(4)
-    tab = torch.zeros((max(K, 1), width), dtype=torch.float32, device=like.device)
-    if len(rows):
-        src = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32)
-                               .reshape(len(rows), width))
-        tab[torch.as_tensor(list(rows), device=like.device)] = src.to(like.device)
-    if collective:
-        dist.all_reduce(tab.view(torch.int32), op=dist.ReduceOp.SUM, group=group)
-    return np.array(_to_host(shard, tab))[:K]
+def _frames_to_medoids(shard, rows):
+    shard.assign_nearest(np.array(rows, dtype=np.float32))
+    # the centers were the medoid frames themselves: every frame's distance is
+    # the distance to the medoid its label names
+    if hasattr(shard, "set_exact"):
+        shard.set_exact(True)
+
+
+def _samples_to_medoids(shard, rows):
+    _assign_shard_to_centers(shard, rows, shard.n_local)
+
+
+# What the k-medoids start has to know about the data it runs on: what the
+# messages call it; whether a warm start needs X_lengths (the reference's rule
+# for frames, kmedoids.py:264-283; samples may also come as flat indices in rank
+# order); the cold start's assignment, (shard, the medoids' rows) -> every row
+# of the shard to its nearest (strict <, the lowest label on ties).
+_Kind = collections.namedtuple("_Kind", "what lengths_required to_medoids")
+_FRAMES = _Kind("frames", True, _frames_to_medoids)
+_SAMPLES = _Kind("samples", False, _samples_to_medoids)
+
+
+def _kmedoids_on_shard(shard, local, lay, kind, n_clusters=None, n_iters=5,
+                       assignments=None, distances=None,
+                       cluster_center_inds=None, X_lengths=None, proposals=None,
+                       random_state=None):
+    """k-medoids over all ranks' shards, the reference's MPI mode
+    (kmedoids.py:133-146 dispatch, :225-283 ``_kmedoids_inputs_tree_mpi``,
+    :365-407 ``ctr_ids_mpi``, sweeps :410-476 / :575-699), for frames and
+    feature samples alike (``kind``); ``local`` holds this rank's rows.
+
+    Warm start: this rank's ``assignments`` / ``distances`` and the same
+    ``cluster_center_inds`` on every rank.  With ``X_lengths`` (the lengths of
+    ALL trajectories, striped over the ranks t % world) they are flat indices
+    into the concatenation of all trajectories or (trajectory, frame) pairs
+    (:func:`ctr_ids_mpi`); without it, where the kind allows that, flat
+    indices in the ranks' order (rank r's after rank r-1's).  Supplying only
+    some of the three raises the reference's ImproperlyConfigured.  Cold start
+    (none of the three; the reference's own branch, :247-262, cannot run --
+    ``np.arange(X)``, ``.append`` on None): ``n_clusters`` distinct indices
+    drawn over ALL ranks' data from a seeded ``np.random.default_rng`` like the
+    single-process path (kmedoids.py:345-352), then everything to its nearest.
+
+    ``proposals``: (rank, local index) pairs, one per cluster (:581-623).
+    Every check that can fail on one rank alone is exchanged first, so that all
+    ranks raise together (:func:`_raise_together`), and the ranks agree on one
+    random stream for the cold start's draw and the sweeps' draws
+    (:func:`_agree_on_seed`).  -> ClusterResult, ``centers`` = the medoids'
+    rows of ``local`` on every rank.  Collective: every rank calls it."""
+    from .exception import DataInvalid, ImproperlyConfigured
+    n_local = lay.hi - lay.lo
+    given = [assignments is not None, distances is not None,
+             cluster_center_inds is not None]
+    warm = all(given)
+    err = None                  # (exception class, message)
+    med, d0, a0 = None, None, None
+    if any(given) and not warm:
+        err = (ImproperlyConfigured,
+               "For KMedoids, MPI mode can start from scratch without "
+               "assignments, distances, or cluster_center_inds. "
+               "Or, it requires that all are supplied.")
+    elif not warm and n_clusters is None:
+        err = (ImproperlyConfigured,
+               "Must provide n_clusters or cluster_center_inds, assignments,"
+               "and distances for KMedoids in MPI mode.")
+    elif warm:
+        try:
+            if X_lengths is None and kind.lengths_required:
+                raise ImproperlyConfigured(
+                    "If cluster_center_inds is given with respect to all data "
+                    "then X_lengths (the lengths of ALL trajectories) also "
+                    "needs to be supplied")
+            if X_lengths is not None:
+                mine_len = sum(int(v) for v in X_lengths[lay.rank::lay.world])
+                if mine_len != n_local:
+                    raise DataInvalid(
+                        "rank %d holds %d %s, but the trajectories X_lengths "
+                        "gives it (t %% %d == %d) have %d"
+                        % (lay.rank, n_local, kind.what, lay.world, lay.rank,
+                           mine_len))
+                med = [int(lay.starts[r]) + i for r, i in
+                       ctr_ids_mpi(cluster_center_inds, X_lengths, lay.world)]
+            elif hasattr(cluster_center_inds[0], "__len__"):
+                raise ImproperlyConfigured(
+                    "If cluster_center_inds is given as [[global_traj_id, "
+                    "frame_id],...] then X_lengths also needs to be supplied")
+            else:
+                med = [int(g) for g in cluster_center_inds]
+                if min(med) < 0 or max(med) >= lay.n_total:
+                    raise IndexError("cluster center index outside the %d %s "
+                                     "of all ranks" % (lay.n_total, kind.what))
+            d0 = np.asarray(distances, dtype=np.float64)
+            a0 = np.asarray(assignments)
+            if len(d0) != n_local or len(a0) != n_local:
+                raise DataInvalid(
+                    "%d assignments / %d distances for %d %s"
+                    % (len(a0), len(d0), n_local, kind.what))
+            mine = [g - lay.lo for g in med if lay.lo <= g < lay.hi]
+            # the medoids must sit at (numerically) zero distance
+            # (kmedoids.py:185-187)
+            if not np.all(d0[mine] < 0.001):
+                raise DataInvalid(
+                    "cluster_center_inds name %s that are not at distance 0 "
+                    "from their cluster's center (max %g)"
+                    % (kind.what, float(np.max(d0[mine]))))
+        except (DataInvalid, ImproperlyConfigured, IndexError) as e:
+            err = (type(e), str(e))
+    K = (len(med) if med is not None else
+         (int(n_clusters) if n_clusters is not None else 0))
+    if err is None and proposals is not None:
+        if len(proposals) != K:
+            err = (DataInvalid,
+                   "Length of 'proposals' didn't match length of 'medoid_inds' "
+                   "({} != {}).".format(len(proposals), K))
+        elif not hasattr(proposals[0], "__len__"):
+            err = (DataInvalid,
+                   "Depth of 'proposals' didn't match 'medoid_inds' "
+                   "(proposals[0] == {}, whereas medoid_inds[0] == {})".format(
+                       proposals[0], (0, 0)))
+    _raise_together(err, (warm, K, proposals is not None, int(n_iters)),
+                    "the start (warm, clusters, proposals given, n_iters)",
+                    lay.group)
+    # one random_state for all: the cold start's draw of the medoids and the
+    # sweeps' draws of members both have to be the same on every rank
+    rs = _agree_on_seed(random_state, lay.group)
+    if warm:
+        shard.set_state(d0, a0.astype(np.int32))
+    else:
+        seed = random_state
+        if not isinstance(seed, (int, np.integer)):
+            seed = rs.randint(0, 2 ** 31 - 1)       # (the agreed stream's)
+        rng = np.random.default_rng(seed=int(seed))
+        med = np.array([])
+        while len(np.unique(med)) < int(n_clusters):
+            med = rng.integers(0, lay.n_total, int(n_clusters))
+        med = [int(g) for g in med]
+        kind.to_medoids(shard, _rows_from_owners(med, local, lay))
+    prop = None
+    if proposals is not None:
+        prop = [int(lay.starts[int(r)]) + int(i) for r, i in proposals]
+    for _ in range(int(n_iters)):
+        med = pam_sweep_sharded(shard, med, proposals=prop, random_state=rs,
+                                group=lay.group)
+    return _cluster_result(shard, lay.pairs(med),
+                           _rows_from_owners(med, local, lay))
 
 
 def kmedoids_sharded(shard, xyz_local, n_iters=5, assignments=None,
                      distances=None, cluster_center_inds=None, X_lengths=None,
                      proposals=None, random_state=None, n_clusters=None,
                      group=None):
-    """k-medoids over all ranks' shards, the reference's MPI mode
-    (kmedoids.py:133-146 dispatch, :225-283 ``_kmedoids_inputs_tree_mpi``,
-    :365-407 ``ctr_ids_mpi``, sweeps :410-476 / :575-699).
-
-    Warm start (what the reference supports there): every rank passes the
-    ``assignments`` / ``distances`` of ITS frames and the same
-    ``cluster_center_inds`` with respect to all data -- flat indices or
-    (trajectory, frame) pairs -- with ``X_lengths`` = the lengths of ALL
-    trajectories; the ranks hold the trajectories striped (t % world).
-    Supplying only some of the three raises the reference's
-    ImproperlyConfigured.  Cold start (none of the three; the reference's own
-    branch, :247-262, cannot run -- ``np.arange(X)``, ``.append`` on None):
-    ``n_clusters`` distinct frames drawn over ALL frames from
-    ``np.random.default_rng(random_state)`` like the single-process path
-    (kmedoids.py:345-352), the same on every rank (rank 0's seed when
-    ``random_state`` is None), then every frame to its nearest.
-
-    ``proposals``: (rank, local index) pairs, one per cluster (:581-623).
+    """k-medoids with metric RMSD over all ranks' ready shards, see
+    :func:`_kmedoids_on_shard`: every rank passes the ``assignments`` /
+    ``distances`` of ITS frames ``xyz_local``; a warm start needs ``X_lengths``.
     Returns (medoids as (rank, local index) pairs, centers float32 [K, A, 3]);
-    labels and distances stay on the shard.  Collective: every rank calls it."""
-    import torch.distributed as dist
-    from .cluster.kcenters import check_random_state
-    from .exception import DataInvalid, ImproperlyConfigured
-    world, rank = _world(group)
-    collective = dist.is_available() and dist.is_initialized()
-    lay = _gather_i64(shard, [shard.offset, shard.n_local], group, world, collective)
-    offs = [int(v) for v in lay[:, 0]]
-    counts = [int(v) for v in lay[:, 1]]
-    n_total = int(sum(counts))
+    labels and distances stay on the shard.  Works without a process group."""
     A = shard.n_atoms
     xyz_local = np.asarray(xyz_local, dtype=np.float32).reshape(-1, A, 3)
-    given = [assignments is not None, distances is not None,
-             cluster_center_inds is not None]
-    if all(given):
-        if X_lengths is None:
-            raise ImproperlyConfigured(
-                "If cluster_center_inds is given with respect to all data then "
-                "X_lengths (the lengths of ALL trajectories) also needs to be "
-                "supplied")
-        if sum(int(v) for v in X_lengths[rank::world]) != counts[rank]:
-            raise DataInvalid(
-                "rank %d holds %d frames, but the trajectories X_lengths gives it "
-                "(t %% %d == %d) have %d" % (rank, counts[rank], world, rank,
-                                            sum(int(v) for v in X_lengths[rank::world])))
-        pairs = ctr_ids_mpi(cluster_center_inds, X_lengths, world)
-        med = [offs[r] + i for r, i in pairs]
-        shard.set_state(np.asarray(distances), np.asarray(assignments))
-        mine = [i for r, i in pairs if r == rank]
-        # the medoids must sit at (numerically) zero distance (kmedoids.py:185-187)
-        if not np.all(np.asarray(distances)[mine] < 0.001):
-            raise DataInvalid(
-                "cluster_center_inds name frames that are not at distance 0 "
-                "from their cluster's center (max %g)"
-                % float(np.max(np.asarray(distances)[mine])))
-    elif not any(given):
-        if n_clusters is None:
-            raise ImproperlyConfigured(
-                "Must provide n_clusters or cluster_center_inds, assignments,"
-                "and distances for KMedoids in MPI mode.")
-        seed = random_state
-        if seed is None or not isinstance(seed, (int, np.integer)):
-            draw = np.random.SeedSequence().entropy % (2 ** 62) if seed is None \
-                else int(check_random_state(seed).randint(0, 2 ** 31 - 1))
-            seed = int(_gather_i64(shard, [draw], group, world, collective)[0, 0])
-        rng = np.random.default_rng(seed=int(seed))
-        med = np.array([])
-        while len(np.unique(med)) < int(n_clusters):
-            med = rng.integers(0, n_total, int(n_clusters))
-        # (global index in the ranks' order: rank r's frames after rank r-1's)
-        bounds = np.cumsum([0] + counts)
-        med = [offs[int(np.searchsorted(bounds, g, side="right") - 1)] +
-               int(g - bounds[int(np.searchsorted(bounds, g, side="right") - 1)])
-               for g in med]
-        rows = [k for k, g in enumerate(med)
-                if offs[rank] <= g < offs[rank] + counts[rank]]
-        ctr = _gather_rows_f32(shard, len(med), 3 * A, rows,
-                               xyz_local[[med[k] - offs[rank] for k in rows]],
-                               group, collective)
-        shard.assign_nearest(ctr.reshape(len(med), A, 3))
-        if hasattr(shard, "set_exact"):
-            shard.set_exact(True)
-    else:
-        raise ImproperlyConfigured(
-            "For KMedoids, MPI mode can start from scratch without "
-            "assignments, distances, or cluster_center_inds. "
-            "Or, it requires that all are supplied.")
-    prop = None
-    if proposals is not None:
-        if len(proposals) != len(med):
-            raise DataInvalid(
-                "Length of 'proposals' didn't match length of 'medoid_inds' "
-                "({} != {}).".format(len(proposals), len(med)))
-        if not hasattr(proposals[0], "__len__"):
-            raise DataInvalid(
-                "Depth of 'proposals' didn't match 'medoid_inds' "
-                "(proposals[0] == {}, whereas medoid_inds[0] == {})".format(
-                    proposals[0], (0, 0)))
-        prop = [offs[int(r)] + int(i) for r, i in proposals]
-    if random_state is None and prop is None:
-        # every rank must draw the same member ranks (the reference agrees on
-        # each draw across ranks, mpi/ops.py randind): rank 0's seed for all
-        draw = int(np.random.SeedSequence().entropy % (2 ** 31 - 1))
-        random_state = int(_gather_i64(shard, [draw], group, world,
-                                       collective)[0, 0])
-    rs = check_random_state(random_state)
-    for _ in range(int(n_iters)):
-        med = pam_sweep_sharded(shard, med, proposals=prop, random_state=rs,
-                                group=group)
-    pairs = []
-    for g in med:
-        r = max(q for q in range(world) if offs[q] <= g and counts[q] > 0
-                and g < offs[q] + counts[q])
-        pairs.append((r, int(g - offs[r])))
-    rows = [k for k, (r, _) in enumerate(pairs) if r == rank]
-    ctr = _gather_rows_f32(shard, len(med), 3 * A, rows,
-                           xyz_local[[pairs[k][1] for k in rows]], group, collective)
-    return pairs, ctr.reshape(len(med), A, 3)
+    res = _kmedoids_on_shard(
+        shard, xyz_local, _Layout.gather(shard.n_local, group), _FRAMES,
+        n_clusters=n_clusters, n_iters=n_iters, assignments=assignments,
+        distances=distances, cluster_center_inds=cluster_center_inds,
+        X_lengths=X_lengths, proposals=proposals, random_state=random_state)
+    return res.center_indices, np.array(res.centers, dtype=np.float32).reshape(
+        len(res.centers), A, 3)
 
 
 # ---------------------------------------------------------------------------
 # estimator-level entry: the reference's mpi_mode
 # ---------------------------------------------------------------------------
-def kmedoids_fit_sharded(traj, n_clusters=None, n_iters=5, assignments=None,
-                         distances=None, cluster_center_inds=None,
-                         X_lengths=None, proposals=None, random_state=None,
-                         group=None):
-    """``kmedoids()`` / ``KMedoids.fit`` when the process group has more than one
-    rank (the reference decides by ``mpi.size() > 1``, kmedoids.py:172): every
-    rank passes ITS OWN frames (the trajectories t % world == rank, one after
-    the other), see ``kmedoids_sharded``.  One process per GPU; the current CUDA
-    device holds the shard.  Returns a ClusterResult like the reference's MPI
-    mode: ``center_indices`` as (rank, local frame index) pairs, this rank's
-    ``assignments`` / ``distances``, the medoids' coordinates on every rank."""
+@contextlib.contextmanager
+def _device_frame_shard(xyz, offset):
+    """The product's shard for RMSD: a FrameStore holding ``xyz`` on a torch
+    stream of its own on the current CUDA device, state reset, the driver
+    running under that stream."""
     import torch
-    import torch.distributed as dist
-    from .cluster import util
-    from .device import FrameStore, as_xyz
-    from .exception import ImproperlyConfigured
-    if not (dist.is_available() and dist.is_initialized()):
-        raise ImproperlyConfigured(
-            "mpi_mode needs an initialised torch.distributed process group "
-            "(one process per GPU, e.g. under torchrun)")
-    xyz = as_xyz(traj)
-    n_local, A = int(xyz.shape[0]), int(xyz.shape[1])
-    world, rank = _world(group)
+    from .device import FrameStore
     device = torch.cuda.current_device()
     tstream = torch.cuda.Stream(device=device)
-    with torch.cuda.stream(tstream):
-        mine = torch.tensor([n_local], dtype=torch.int64, device="cuda")
-        everyone = torch.empty(world, dtype=torch.int64, device="cuda")
-        dist.all_gather_into_tensor(everyone, mine, group=group)
-        counts = [int(c) for c in everyone.cpu().numpy()]
-    starts = np.concatenate([[0], np.cumsum(counts)])
-    with FrameStore(n_local, A, device=device, global_offset=int(starts[rank]),
+    with FrameStore(int(xyz.shape[0]), int(xyz.shape[1]), device=device,
+                    global_offset=int(offset),
                     stream=tstream.cuda_stream) as store:
         store.load(xyz)
         store.reset_state()
-        shard = DeviceShard(store)
         with torch.cuda.stream(tstream):
-            pairs, ctr = kmedoids_sharded(
-                shard, xyz, n_iters=n_iters, assignments=assignments,
-                distances=distances, cluster_center_inds=cluster_center_inds,
-                X_lengths=X_lengths, proposals=proposals,
-                random_state=random_state, n_clusters=n_clusters, group=group)
-        d, a = store.download_state()
-    return util.ClusterResult(
-        center_indices=pairs, assignments=a.astype(np.int64),
-        distances=d.astype(np.float64),
-        centers=[ctr[k].copy() for k in range(len(pairs))])
+            yield DeviceShard(store)
+
+
+def kmedoids_fit_sharded(traj, n_clusters=None, n_iters=5, assignments=None,
+                         distances=None, cluster_center_inds=None,
+                         X_lengths=None, proposals=None, random_state=None,
+                         group=None, make_shard=None):
+    """``kmedoids()`` / ``KMedoids.fit`` when the process group has more than one
+    rank (the reference decides by ``mpi.size() > 1``, kmedoids.py:172): every
+    rank passes ITS OWN frames (the trajectories t % world == rank, one after
+    the other), see :func:`_kmedoids_on_shard`.  One process per GPU; the
+    current CUDA device holds the shard (``make_shard(xyz, offset)`` -> a
+    context manager yielding another one: tests plug in a host shard).
+    Returns a ClusterResult like the reference's MPI mode: ``center_indices``
+    as (rank, local frame index) pairs, this rank's ``assignments`` /
+    ``distances``, the medoids' coordinates on every rank."""
+    from .device import as_xyz
+    _need_group()
+    xyz = as_xyz(traj)
+    lay = _Layout.gather(len(xyz), group)
+    with (make_shard or _device_frame_shard)(xyz, lay.lo) as shard:
+        return _kmedoids_on_shard(
+            shard, xyz, lay, _FRAMES, n_clusters=n_clusters, n_iters=n_iters,
+            assignments=assignments, distances=distances,
+            cluster_center_inds=cluster_center_inds, X_lengths=X_lengths,
+            proposals=proposals, random_state=random_state)
 
 
 def fit_sharded(traj, n_clusters=None, dist_cutoff=0.0, n_iters=0,
                 random_state=None, group=None, use_triangle_inequality=False,
-                init_centers=None):
+                init_centers=None, make_shard=None):
     """k-centers (+ ``n_iters`` PAM sweeps) where every rank of the initialised
     ``torch.distributed`` group passes ITS OWN frames -- what ``mpi_mode=True``
     means in the reference (kcenters.py:314-378, kmedoids.py MPI branch): rank
     r's frames follow rank r-1's in the global order, ties go to the lowest
-    rank.  One process per GPU; the current CUDA device holds the shard.
+    rank.  One process per GPU; the current CUDA device holds the shard
+    (``make_shard``: as for :func:`kmedoids_fit_sharded`).
 
     Returns a ClusterResult like the reference's MPI mode: ``center_indices``
     as (rank, local frame index) pairs (kcenters.py:375-376), ``assignments`` /
     ``distances`` for this rank's frames, ``centers`` = the centers'
     coordinates (float32 [A, 3] each), the same list on every rank.
     ``random_state`` and ``init_centers`` (a warm start, kcenters.py:200-206:
-    see ``warm_start_sharded``) must be the same on every rank."""
-    import torch
-    import torch.distributed as dist
-    from .cluster import util
-    from .cluster.kcenters import check_random_state
-    from .device import FrameStore, as_xyz
+    see ``warm_start_sharded``) must be the same on every rank; the sweeps'
+    random stream is agreed on first (:func:`_agree_on_seed`)."""
+    from .device import as_xyz
     from .exception import ImproperlyConfigured
-    if not (dist.is_available() and dist.is_initialized()):
-        raise ImproperlyConfigured(
-            "mpi_mode needs an initialised torch.distributed process group "
-            "(one process per GPU, e.g. under torchrun)")
+    _need_group()
     xyz = as_xyz(traj)
-    n_local, A = int(xyz.shape[0]), int(xyz.shape[1])
-    world, rank = _world(group)
-    device = torch.cuda.current_device()
-    tstream = torch.cuda.Stream(device=device)
-    rs = check_random_state(random_state)
-    with torch.cuda.stream(tstream):
-        # where this rank's block starts in the global order
-        mine = torch.tensor([n_local], dtype=torch.int64, device="cuda")
-        everyone = torch.empty(world, dtype=torch.int64, device="cuda")
-        dist.all_gather_into_tensor(everyone, mine, group=group)
-        counts = [int(c) for c in everyone.cpu().numpy()]
-    starts = np.concatenate([[0], np.cumsum(counts)])
-    n_total = int(starts[-1])
-    if n_total == 0:
+    A = int(xyz.shape[1])
+    lay = _Layout.gather(len(xyz), group)
+    if lay.n_total == 0:
         raise ValueError("cannot cluster an empty trajectory")
     if n_clusters is None or np.isinf(n_clusters):
         if not dist_cutoff:
             raise ImproperlyConfigured("Either n_clusters or cluster_radius "
                                        "is required for KHybrid clustering")
-        max_new = 2 * n_total + 16
+        max_new = 2 * lay.n_total + 16
     else:
         max_new = int(n_clusters)
-    with FrameStore(n_local, A, device=device, global_offset=int(starts[rank]),
-                    stream=tstream.cuda_stream) as store:
-        store.load(xyz)
-        store.reset_state()
-        shard = DeviceShard(store)
-        with torch.cuda.stream(tstream):
-            med = []
-            if init_centers is not None:
-                med = warm_start_sharded(shard, init_centers, group=group)
-                # (the shards' tables of accepted centers would lack these: the
-                # tile skip is an optimisation only, results do not change)
-                use_triangle_inequality = False
-            idx, _ = kcenters_sharded(
-                shard, len(med), max(0, max_new - len(med)),
-                float(dist_cutoff or 0.0), group=group,
-                use_triangle_inequality=use_triangle_inequality)
-            med = med + [int(g) for g in idx]
-            for _ in range(int(n_iters)):
-                med = pam_sweep_sharded(shard, med, random_state=rs,
-                                        group=group)
-            # the centers' own coordinates, from their owners
-            K = len(med)
-            tab = torch.zeros((max(K, 1), 3 * A), dtype=torch.float32,
-                              device="cuda")
-            lo, hi = int(starts[rank]), int(starts[rank + 1])
-            rows = [r for r, g in enumerate(med) if lo <= g < hi]
-            if rows:
-                loc = torch.from_numpy(np.ascontiguousarray(
-                    xyz[[med[r] - lo for r in rows]].reshape(len(rows), -1)))
-                tab[torch.tensor(rows, device="cuda")] = loc.to("cuda")
-            dist.all_reduce(tab.view(torch.int32), op=dist.ReduceOp.SUM,
-                            group=group)
-            centers_xyz = tab.cpu().numpy()
-        d, a = store.download_state()
-    pairs = []
-    for g in med:
-        r = int(np.searchsorted(starts, g, side="right") - 1)
-        pairs.append((r, int(g - starts[r])))
-    centers = [centers_xyz[k].reshape(A, 3).copy() for k in range(len(med))]
+    rs = _agree_on_seed(random_state, group) if int(n_iters) > 0 else None
+    kept = ()
     if init_centers is not None and int(n_iters) == 0:
         # k-centers alone returns the caller's initial centers followed by the
         # new ones (kcenters.py:200-240: `centers` starts as init_centers, and
@@ -1281,14 +1363,19 @@ def fit_sharded(traj, n_clusters=None, dist_cutoff=0.0, n_iters=0,
         # than `centers` and the new labels start at len(center_indices),
         # kcenters.py:306: the reference's own misalignment, reproduced like the
         # single-process path does)
-        n_new = len(idx)
-        centers = ([np.asarray(as_xyz(c_)[0] if np.ndim(c_) == 3 else c_,
-                               dtype=np.float32).reshape(A, 3).copy()
-                    for c_ in init_centers] +
-                   (centers[len(med) - n_new:] if n_new else []))
-    return util.ClusterResult(
-        center_indices=pairs, assignments=a.astype(np.int64),
-        distances=d.astype(np.float64), centers=centers)
+        kept = [np.asarray(as_xyz(c_)[0] if np.ndim(c_) == 3 else c_,
+                           dtype=np.float32).reshape(A, 3).copy()
+                for c_ in init_centers]
+    with (make_shard or _device_frame_shard)(xyz, lay.lo) as shard:
+        med = []
+        if init_centers is not None:
+            med = warm_start_sharded(shard, init_centers, group=group)
+            # (the shards' tables of accepted centers would lack these: the
+            # tile skip is an optimisation only, results do not change)
+            use_triangle_inequality = False
+        return _fit_on_shard(shard, xyz, lay, med, max(0, max_new - len(med)),
+                             dist_cutoff, n_iters, rs, kept,
+                             use_triangle_inequality)
 
 
 # ---------------------------------------------------------------------------
@@ -1341,86 +1428,38 @@ def _assign_shard_to_centers(shard, centers, n_local):
     return d, a
 
 
+@contextlib.contextmanager
 def _device_feature_shard(Xw, metric_id, offset):
     """The product's shard: a FeatureStore on a torch stream of its own on the
     current CUDA device, the driver running under that stream."""
-    import contextlib
     import torch
     from .geometry.libdist import FeatureStore
-
-    @contextlib.contextmanager
-    def cm():
-        device = torch.cuda.current_device()
-        tstream = torch.cuda.Stream(device=device)
-        with FeatureStore.from_array(Xw, metric_id, device=device,
-                                     global_offset=offset,
-                                     stream=tstream.cuda_stream) as store:
-            with torch.cuda.stream(tstream):
-                yield FeatureShard(store, metric_id)
-    return cm()
+    device = torch.cuda.current_device()
+    tstream = torch.cuda.Stream(device=device)
+    with FeatureStore.from_array(Xw, metric_id, device=device,
+                                 global_offset=offset,
+                                 stream=tstream.cuda_stream) as store:
+        with torch.cuda.stream(tstream):
+            yield FeatureShard(store, metric_id)
 
 
 _PAM_WHAT = "the sharded PAM sweep"
 
 
-def _agree_on_seed(random_state, group, world):
-    """The sweeps draw member ranks from ONE stream that every rank replays
-    (the reference agrees on each draw, mpi/ops.py randind): ranks that pass
-    different seeds or differently positioned RandomStates would propose
-    different samples and wait for each other forever, so they compare first
-    and raise ImproperlyConfigured together.  None everywhere (also the global
-    numpy RandomState, what the estimators make of None): rank 0's draw for
-    all.  -> RandomState"""
-    import hashlib
-    import torch.distributed as dist
-    from .cluster.kcenters import check_random_state
-    from .exception import ImproperlyConfigured
-    if random_state is None or random_state is np.random.mtrand._rand:
-        mark = None
-    elif isinstance(random_state, (int, np.integer)):
-        mark = ("seed", int(random_state))
-    elif isinstance(random_state, np.random.RandomState):
-        st = random_state.get_state()
-        mark = ("state", hashlib.sha1(np.asarray(st[1]).tobytes()).hexdigest(),
-                int(st[2]))
-    else:
-        mark = ("other", repr(random_state))
-    draw = int(np.random.SeedSequence().entropy % (2 ** 31 - 1))
-    everyone = [None] * world
-    dist.all_gather_object(everyone, (mark, draw), group=group)
-    if len(set(m for m, _ in everyone)) != 1:
-        raise ImproperlyConfigured(
-            "the ranks disagree on random_state (%s): the sharded PAM sweep "
-            "needs the same seed, or identically seeded RandomStates, on "
-            "every rank" % ", ".join(
-                "rank %d: %s" % (r, "None" if m is None else m[0] + " " +
-                                 str(m[1])[:12]) for r, (m, _) in
-                enumerate(everyone)))
-    if mark is None:
-        return check_random_state(everyone[0][1])
-    return check_random_state(random_state)
-
-
 def _agree_on_samples(X, metric_id, group, what="mpi_mode"):
     """The pre-loop agreement of the feature drivers: the ranks compare
     (n_features, dtype, metric, data usable) and raise TOGETHER, see
-    :func:`fit_features_sharded`.  -> (world, rank, starts int64 [world + 1])"""
-    import torch.distributed as dist
+    :func:`fit_features_sharded`.  -> the :class:`_Layout` of the samples"""
     from .exception import DataInvalid, ImproperlyConfigured
-    if not (dist.is_available() and dist.is_initialized()):
-        raise ImproperlyConfigured(
-            "%s needs an initialised torch.distributed process group "
-            "(one process per GPU, e.g. under torchrun)" % what)
+    _need_group(what)
     if metric_id not in METRIC_NAMES:
         raise ImproperlyConfigured("not a device feature metric: %r"
                                    % (metric_id,))
-    world, rank = _world(group)
     problem = _feature_data_problem(X, metric_id)
     mine = (int(X.shape[0]) if problem is None else 0,
             int(X.shape[1]) if problem is None else -1,
             str(X.dtype) if problem is None else "", int(metric_id), problem)
-    everyone = [None] * world
-    dist.all_gather_object(everyone, mine, group=group)
+    everyone = _everyone(mine, group)
     bad = [(r, e[4]) for r, e in enumerate(everyone) if e[4] is not None]
     if bad:
         raise DataInvalid(
@@ -1433,12 +1472,10 @@ def _agree_on_samples(X, metric_id, group, what="mpi_mode"):
             % ", ".join("rank %d: (%d, %s, %s)"
                         % (r, e[1], e[2], METRIC_NAMES.get(e[3], e[3]))
                         for r, e in enumerate(everyone)))
-    counts = [e[0] for e in everyone]
-    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    n_total = int(starts[-1])
-    if n_total == 0:
+    lay = _Layout([e[0] for e in everyone], group)
+    if lay.n_total == 0:
         raise ValueError("cannot cluster an empty set of samples")
-    return world, rank, starts
+    return lay
 
 
 def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
@@ -1474,54 +1511,22 @@ def fit_features_sharded(X, metric_id, n_clusters=None, dist_cutoff=0.0,
     offset)`` -> a context manager yielding the shard (tests plug in a
     numpy-backed one); the default puts the samples on the current CUDA
     device."""
-    import torch.distributed as dist
-    from .cluster import util
-    world, rank, starts = _agree_on_samples(
-        X, metric_id, group, _PAM_WHAT if n_iters else "mpi_mode")
-    n_total = int(starts[-1])
-    rs = (_agree_on_seed(random_state, group, world) if int(n_iters) > 0
-          else None)
-    lo, hi = int(starts[rank]), int(starts[rank + 1])
-    if make_shard is None:
-        make_shard = _device_feature_shard
-    with make_shard(X, metric_id, lo) as shard:
+    lay = _agree_on_samples(X, metric_id, group,
+                            _PAM_WHAT if n_iters else "mpi_mode")
+    rs = _agree_on_seed(random_state, group) if int(n_iters) > 0 else None
+    with (make_shard or _device_feature_shard)(X, metric_id, lay.lo) as shard:
         if init_centers is None:
             centers, med = [], []
             shard.reset_state()
         else:
             centers = [c for c in init_centers]
-            d, a = _assign_shard_to_centers(shard, centers, hi - lo)
-            med = _closest_members(d, a, lo, len(centers), group)
+            d, a = _assign_shard_to_centers(shard, centers, lay.hi - lay.lo)
+            med = _closest_members(d, a, lay.lo, len(centers), group)
         budget = (np.inf if n_clusters is None else n_clusters) - len(med)
         max_new = (0 if budget <= 0 else
-                   (2 * n_total + 16 if np.isinf(budget) else int(budget)))
-        idx, _ = kcenters_sharded(shard, len(med), max_new,
-                                  float(dist_cutoff or 0.0), group=group)
-        med = med + [int(g) for g in idx]
-        for _ in range(int(n_iters)):
-            med = pam_sweep_sharded(shard, med, random_state=rs, group=group)
-        d, a = shard.state()
-    # the new centers' rows (after PAM sweeps: every medoid's), from their
-    # owners, in X's dtype
-    first_new = 0 if int(n_iters) > 0 else len(med) - len(idx)
-    rows = {k: X[med[k] - lo].copy() for k in range(first_new, len(med))
-            if lo <= med[k] < hi}
-    tables = [None] * world
-    dist.all_gather_object(tables, rows, group=group)
-    for t in tables:
-        rows.update(t)
-    new_centers = [rows[k] for k in range(first_new, len(med))]
-    if init_centers is None or int(n_iters) > 0:
-        centers = new_centers
-    else:
-        centers = centers + new_centers
-    pairs = []
-    for g in med:
-        r = int(np.searchsorted(starts, g, side="right") - 1)
-        pairs.append((r, int(g - starts[r])))
-    return util.ClusterResult(
-        center_indices=pairs, assignments=np.asarray(a).astype(np.int64),
-        distances=np.asarray(d, dtype=np.float64), centers=centers)
+                   (2 * lay.n_total + 16 if np.isinf(budget) else int(budget)))
+        return _fit_on_shard(shard, X, lay, med, max_new, dist_cutoff, n_iters,
+                             rs, centers)
 
 
 def kmedoids_features_sharded(X, metric_id, n_clusters=None, n_iters=5,
@@ -1532,151 +1537,15 @@ def kmedoids_features_sharded(X, metric_id, n_clusters=None, n_iters=5,
     """``kmedoids()`` / ``KMedoids.fit`` in mpi_mode for a feature metric
     (``metric_id`` 0 euclidean, 1 manhattan, 2 hamming): every rank passes ITS
     OWN samples [n_local, n_features], the counterpart of
-    :func:`kmedoids_sharded` for RMSD with the same two starts.
+    :func:`kmedoids_fit_sharded` for RMSD with the same two starts
+    (:func:`_kmedoids_on_shard`); a warm start may also name its medoids
+    without ``X_lengths``, as flat indices in the ranks' order.  Returns a
+    ClusterResult shaped like :func:`fit_features_sharded`'s."""
+    lay = _agree_on_samples(X, metric_id, group, _PAM_WHAT)
+    with (make_shard or _device_feature_shard)(X, metric_id, lay.lo) as shard:
+        return _kmedoids_on_shard(
+            shard, X, lay, _SAMPLES, n_clusters=n_clusters, n_iters=n_iters,
+            assignments=assignments, distances=distances,
+            cluster_center_inds=cluster_center_inds, X_lengths=X_lengths,
+            proposals=proposals, random_state=random_state)
 
-    Warm start: this rank's ``assignments`` / ``distances`` and the same
-    ``cluster_center_inds`` on every rank.  With ``X_lengths`` (the lengths of
-    ALL trajectories, striped over the ranks t % world) they are flat indices
-    into the concatenation of all trajectories or (trajectory, frame) pairs
-    (:func:`ctr_ids_mpi`); without it, flat indices in the ranks' order (rank
-    r's samples after rank r-1's).  Cold start: ``n_clusters`` distinct samples
-    from ``np.random.default_rng(seed)`` over all samples like the
-    single-process path, then every sample to its nearest (strict <, lowest
-    label on ties).  Supplying only some of the three raises the reference's
-    ImproperlyConfigured.
-
-    ``proposals``: (rank, local index) pairs, one per cluster.  Returns a
-    ClusterResult shaped like :func:`fit_features_sharded`'s.  Collective:
-    every rank calls it, and every check that can fail on one rank alone is
-    exchanged first so that all ranks raise together."""
-    import torch.distributed as dist
-    from .cluster import util
-    from .cluster.kcenters import check_random_state
-    from .exception import DataInvalid, ImproperlyConfigured
-    world, rank, starts = _agree_on_samples(X, metric_id, group, _PAM_WHAT)
-    n_total = int(starts[-1])
-    lo, hi = int(starts[rank]), int(starts[rank + 1])
-    # every check of this rank's own arguments is exchanged before anyone
-    # raises: a rank raising alone would leave the others in a collective
-    given = [assignments is not None, distances is not None,
-             cluster_center_inds is not None]
-    warm = all(given)
-    err = None                  # (exception class, message)
-    med, d0, a0 = None, None, None
-    if any(given) and not warm:
-        err = (ImproperlyConfigured,
-               "For KMedoids, MPI mode can start from scratch without "
-               "assignments, distances, or cluster_center_inds. "
-               "Or, it requires that all are supplied.")
-    elif not warm and n_clusters is None:
-        err = (ImproperlyConfigured,
-               "Must provide n_clusters or cluster_center_inds, assignments,"
-               "and distances for KMedoids in MPI mode.")
-    elif warm:
-        try:
-            if X_lengths is not None:
-                mine_len = sum(int(v) for v in X_lengths[rank::world])
-                if mine_len != hi - lo:
-                    raise DataInvalid(
-                        "rank %d holds %d samples, but the trajectories "
-                        "X_lengths gives it (t %% %d == %d) have %d"
-                        % (rank, hi - lo, world, rank, mine_len))
-                pairs0 = ctr_ids_mpi(cluster_center_inds, X_lengths, world)
-                med = [int(starts[r]) + i for r, i in pairs0]
-            elif hasattr(cluster_center_inds[0], "__len__"):
-                raise ImproperlyConfigured(
-                    "If cluster_center_inds is given as [[global_traj_id, "
-                    "frame_id],...] then X_lengths also needs to be supplied")
-            else:
-                med = [int(g) for g in cluster_center_inds]
-                if min(med) < 0 or max(med) >= n_total:
-                    raise IndexError("cluster center index outside the %d "
-                                     "samples of all ranks" % n_total)
-            d0 = np.asarray(distances, dtype=np.float64)
-            a0 = np.asarray(assignments)
-            if len(d0) != hi - lo or len(a0) != hi - lo:
-                raise DataInvalid(
-                    "rank %d: %d assignments / %d distances for %d samples"
-                    % (rank, len(a0), len(d0), hi - lo))
-            mine = [g - lo for g in med if lo <= g < hi]
-            # the medoids must sit at (numerically) zero distance
-            # (kmedoids.py:185-187)
-            if not np.all(d0[mine] < 0.001):
-                raise DataInvalid(
-                    "rank %d: cluster_center_inds name samples that are not "
-                    "at distance 0 from their cluster's center (max %g)"
-                    % (rank, float(np.max(d0[mine]))))
-        except (DataInvalid, ImproperlyConfigured, IndexError) as e:
-            err = (type(e), str(e))
-    K = (len(med) if med is not None else
-         (int(n_clusters) if n_clusters is not None else 0))
-    if err is None and proposals is not None:
-        if len(proposals) != K:
-            err = (DataInvalid,
-                   "Length of 'proposals' didn't match length of 'medoid_inds' "
-                   "({} != {}).".format(len(proposals), K))
-        elif not hasattr(proposals[0], "__len__"):
-            err = (DataInvalid,
-                   "Depth of 'proposals' didn't match 'medoid_inds' "
-                   "(proposals[0] == {}, whereas medoid_inds[0] == {})".format(
-                       proposals[0], (0, 0)))
-    said = [None] * world
-    dist.all_gather_object(
-        said, (err, warm, K, proposals is not None, int(n_iters)), group=group)
-    bad = [(r, e[0]) for r, e in enumerate(said) if e[0] is not None]
-    if bad:
-        raise bad[0][1][0]("; ".join(
-            m if m.startswith("rank ") else "rank %d: %s" % (r, m)
-            for r, (_, m) in bad))
-    if len(set(e[1:] for e in said)) != 1:
-        raise ImproperlyConfigured(
-            "the ranks disagree on the start (warm, clusters, proposals given, "
-            "n_iters): %s" % ", ".join("rank %d: %s" % (r, e[1:])
-                                       for r, e in enumerate(said)))
-    # one random_state for all: the cold start's draw of the medoids and the
-    # sweeps' draws of members both have to be the same on every rank
-    rs = _agree_on_seed(random_state, group, world)
-    if not warm:
-        seed = random_state
-        if seed is None or not isinstance(seed, (int, np.integer)):
-            draw = (np.random.SeedSequence().entropy % (2 ** 62) if seed is None
-                    else int(check_random_state(seed).randint(0, 2 ** 31 - 1)))
-            seeds = [None] * world
-            dist.all_gather_object(seeds, int(draw), group=group)
-            seed = seeds[0]
-        rng = np.random.default_rng(seed=int(seed))
-        med = np.array([])
-        while len(np.unique(med)) < int(n_clusters):
-            med = rng.integers(0, n_total, int(n_clusters))
-        med = [int(g) for g in med]
-    prop = None
-    if proposals is not None:
-        prop = [int(starts[int(r)]) + int(i) for r, i in proposals]
-
-    def rows_of(which):
-        rows = {k: X[g - lo].copy() for k, g in enumerate(which)
-                if lo <= g < hi}
-        tables = [None] * world
-        dist.all_gather_object(tables, rows, group=group)
-        for t in tables:
-            rows.update(t)
-        return [rows[k] for k in range(len(which))]
-
-    if make_shard is None:
-        make_shard = _device_feature_shard
-    with make_shard(X, metric_id, lo) as shard:
-        if warm:
-            shard.set_state(d0, a0.astype(np.int32))
-        else:
-            _assign_shard_to_centers(shard, rows_of(med), hi - lo)
-        for _ in range(int(n_iters)):
-            med = pam_sweep_sharded(shard, med, proposals=prop, random_state=rs,
-                                    group=group)
-        d, a = shard.state()
-    pairs = []
-    for g in med:
-        r = int(np.searchsorted(starts, g, side="right") - 1)
-        pairs.append((r, int(g - starts[r])))
-    return util.ClusterResult(
-        center_indices=pairs, assignments=np.asarray(a).astype(np.int64),
-        distances=np.asarray(d, dtype=np.float64), centers=rows_of(med))

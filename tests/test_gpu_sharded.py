@@ -668,6 +668,66 @@ def test_kmedoids_in_mpi_mode(tmp_path, world, backend):
             np.concatenate([p[key + "_d"] for p in parts]), wd)
 
 
+# ---- KHybrid in MPI mode with the estimator's default random_state ------------------
+_CHILD5 = _CHILD3[:_CHILD3.index("from enspara_amd import sharded, synth")] + r"""
+from enspara_amd import sharded, synth
+from enspara_amd.cluster import KHybrid
+n, A, K = 600, 14, 6
+x = synth.synth(n, A, 7, seed=17)
+lo, cnt = sharded.shard_bounds(n, world, rank)
+np.random.seed(1000 + rank)             # (nothing shared by accident)
+hy = KHybrid("rmsd", n_clusters=K, kmedoids_updates=1, mpi_mode=True).fit(x[lo:lo + cnt])
+np.savez(out + ".%d.npz" % rank, lo=lo, ci=np.array(hy.center_indices_),
+         a=hy.labels_, d=hy.distances_, c=np.array(hy.centers_))
+dist.barrier()
+dist.destroy_process_group()
+"""
+
+
+def test_khybrid_in_mpi_mode_without_a_random_state(tmp_path):
+    """KHybrid's default random_state is numpy's global stream, seeded
+    differently on every rank: the ranks agree on one stream before the sweep
+    (sharded._agree_on_seed) -- identical medoids on both ranks, every frame's
+    distance the RMSD to the medoid its label names"""
+    import socket
+    from oracle import qcp
+    world = 2
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = str(s.getsockname()[1])
+    s.close()
+    out = str(tmp_path / "r")
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    procs = [subprocess.Popen([sys.executable, "-c", _CHILD5, ROOT, str(r),
+                               str(world), port, out, "gloo"], env=env,
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                              text=True) for r in range(world)]
+    try:
+        logs = [p.communicate(timeout=120)[0] for p in procs]
+    except subprocess.TimeoutExpired:
+        for p in procs:
+            p.kill()
+        pytest.fail("a rank hung: 120 s without both ranks returning")
+    for p, log in zip(procs, logs):
+        assert p.returncode == 0, log[-4000:]
+    parts = [np.load(out + ".%d.npz" % r) for r in range(world)]
+    x = synth.synth(600, 14, 7, seed=17)
+    los = [int(p["lo"]) for p in parts]
+    med = [los[int(r)] + int(i) for r, i in parts[0]["ci"]]
+    assert len(set(med)) == 6
+    for p in parts:
+        assert [los[int(r)] + int(i) for r, i in p["ci"]] == med
+        np.testing.assert_array_equal(p["c"], x[med])
+    a = np.concatenate([p["a"] for p in parts])
+    d = np.concatenate([p["d"] for p in parts])
+    for k, g in enumerate(med):
+        sel = np.flatnonzero(a == k)
+        np.testing.assert_array_equal(
+            d[sel].astype(np.float32),
+            qcp.rmsd(x, x[int(g)])[sel].astype(np.float32))
+
+
 def test_bench_two_ranks_on_one_device(tmp_path):
     """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, one
     process per rank), with EK_BENCH_ONE_DEVICE=1: both ranks on device 0 and a

@@ -846,3 +846,200 @@ def test_tied_warm_start_and_khybrid_across_ranks(which):
         np.testing.assert_array_equal(
             np.concatenate([p[name + "_dist"] for p in parts]).astype(np.float64),
             wd, name)
+
+
+# ---- the estimator-level RMSD entries on host shards (make_shard=) -----------------------
+_EST_N, _EST_A, _EST_K = 300, 8, 4      # two ranks: 256 + 44 frames
+_EST_LIMIT = 240
+
+
+def _spawn_limited(fn, world, args):
+    """every rank has to come back: a rank left waiting in a collective fails
+    the test instead of hanging the suite"""
+    import time
+    ctx = mp.spawn(fn, args=(world, _free_port()) + args, nprocs=world,
+                   join=False)
+    deadline = time.time() + _EST_LIMIT
+    while not ctx.join(timeout=5):
+        if time.time() > deadline:
+            for p in ctx.processes:
+                p.kill()
+            pytest.fail("a rank hung: %d s without all ranks returning"
+                        % _EST_LIMIT)
+
+
+def _est_setup(rank, world, port):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import contextlib
+    from enspara_amd import sharded, synth
+    from _host_shard import HostShard
+    _few_threads()
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port,
+                            rank=rank, world_size=world)
+    x = synth.synth(_EST_N, _EST_A, 4, seed=2)
+    lo, cnt = sharded.shard_bounds(_EST_N, world, rank)
+
+    @contextlib.contextmanager
+    def host(xyz, offset):
+        yield HostShard(xyz, offset)
+    return sharded, x, lo, cnt, host
+
+
+def _est_init(x):
+    """frames of both shards, one of them twice (the second copy attracts
+    nothing) and a structure far from all"""
+    return [x[5], x[280], x[100], x[5], (x[0] * 7.0 + 3.0).astype(np.float32)]
+
+
+def _est_error_worker(rank, world, port, outdir):
+    sharded, x, lo, cnt, _ = _est_setup(rank, world, port)
+    from _host_shard import HostShard
+    mine = x[lo:lo + cnt]
+    seen = []
+
+    def attempt(name, **kw):
+        try:
+            sharded.kmedoids_sharded(HostShard(mine, lo), mine, n_iters=1, **kw)
+            seen.append("%s\tnone\t" % name)
+        except Exception as e:
+            seen.append("%s\t%s\t%s" % (name, type(e).__name__, e))
+
+    attempt("seed", n_clusters=_EST_K, random_state=None if rank else 3)
+    if rank == 1:
+        attempt("some", n_clusters=_EST_K, random_state=1,
+                assignments=np.zeros(cnt, dtype=np.int64))
+    else:
+        attempt("some", n_clusters=_EST_K, random_state=1)
+    # the trajectories striped t % 2: [256] on rank 0, [44] on rank 1
+    attempt("lengths", assignments=np.zeros(cnt, dtype=np.int64),
+            distances=np.zeros(cnt), cluster_center_inds=[0], random_state=1,
+            X_lengths=[256, 40] if rank == 1 else [256, 44])
+    with open(os.path.join(outdir, "r%d.txt" % rank), "w") as f:
+        f.write("\n".join(seen))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_kmedoids_sharded_raises_on_every_rank():
+    """arguments that are wrong, or differ, on ONE rank: every rank raises the
+    same class and nobody is left in a collective -- ranks that disagree on
+    random_state (one None, one a seed), one rank with only `assignments`, one
+    rank whose X_lengths do not add up to its frames"""
+    with tempfile.TemporaryDirectory() as d:
+        _spawn_limited(_est_error_worker, 2, (d,))
+        seen = [[line.split("\t") for line in
+                 open(os.path.join(d, "r%d.txt" % r)).read().split("\n")]
+                for r in range(2)]
+    for s in seen:
+        assert [(n, c) for n, c, _ in s] == [
+            ("seed", "ImproperlyConfigured"), ("some", "ImproperlyConfigured"),
+            ("lengths", "DataInvalid")]
+        assert "can start from scratch" in s[1][2] and "rank 1" in s[1][2]
+        assert "rank 1 holds 44 frames" in s[2][2]
+
+
+def _est_fit_worker(rank, world, port, outdir):
+    sharded, x, lo, cnt, host = _est_setup(rank, world, port)
+    mine = x[lo:lo + cnt]
+    np.random.seed(1000 + rank)         # (nothing shared by accident)
+    runs = {
+        "none": sharded.fit_sharded(mine, n_clusters=_EST_K, n_iters=1,
+                                    random_state=None, make_shard=host),
+        "hy": sharded.fit_sharded(mine, n_clusters=_EST_K, n_iters=1,
+                                  random_state=4, make_shard=host),
+        "ws": sharded.fit_sharded(mine, n_clusters=_EST_K + 2, n_iters=0,
+                                  init_centers=_est_init(x), make_shard=host),
+        "km": sharded.kmedoids_fit_sharded(mine, n_clusters=_EST_K, n_iters=2,
+                                           random_state=7, make_shard=host),
+    }
+    out = {"lo": lo}
+    for key, res in runs.items():
+        out[key + "_ci"] = np.array(res.center_indices).reshape(-1, 2)
+        out[key + "_a"], out[key + "_d"] = res.assignments, res.distances
+        out[key + "_c"] = np.array(res.centers)
+    np.savez(os.path.join(outdir, "r%d.npz" % rank), **out)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.fixture(scope="module")
+def est_parts():
+    with tempfile.TemporaryDirectory() as d:
+        _spawn_limited(_est_fit_worker, 2, (d,))
+        return [dict(np.load(os.path.join(d, "r%d.npz" % r))) for r in range(2)]
+
+
+def _est_medoids(parts, key):
+    los = [int(p["lo"]) for p in parts]
+    med = [los[int(r)] + int(i) for r, i in parts[0][key + "_ci"]]
+    for p in parts:
+        assert [los[int(r)] + int(i) for r, i in p[key + "_ci"]] == med
+    return med
+
+
+def test_fit_sharded_without_a_random_state(est_parts):
+    """k-hybrid with random_state=None on every rank (what the estimator's
+    default comes to) and differently seeded global streams: the ranks still
+    draw the same proposals -- identical medoids on both ranks, every frame's
+    distance the RMSD to the medoid its label names"""
+    from oracle import qcp
+    from enspara_amd import synth
+    x = synth.synth(_EST_N, _EST_A, 4, seed=2)
+    med = _est_medoids(est_parts, "none")
+    assert len(set(med)) == _EST_K
+    for p in est_parts:
+        np.testing.assert_array_equal(p["none_c"], x[med])
+    a = np.concatenate([p["none_a"] for p in est_parts])
+    d = np.concatenate([p["none_d"] for p in est_parts])
+    for k, g in enumerate(med):
+        sel = np.flatnonzero(a == k)
+        np.testing.assert_array_equal(
+            d[sel].astype(np.float32),
+            qcp.rmsd(x, x[int(g)])[sel].astype(np.float32))
+
+
+def test_rmsd_estimator_entries_on_host_shards(est_parts):
+    """fit_sharded (k-hybrid; k-centers alone from a warm start) and
+    kmedoids_fit_sharded (cold start) through make_shard=: center indices,
+    labels, float64 distances and the centers' coordinates of the
+    single-process oracle"""
+    from oracle import cluster as oc
+    from enspara_amd import synth
+    x = synth.synth(_EST_N, _EST_A, 4, seed=2)
+    K = _EST_K
+    inds, a, d = oc.kcenters(x, n_clusters=K)
+    hy = oc.pam_update(x, inds, a, d, random_state=np.random.RandomState(4))
+    init = _est_init(x)
+    wi, wa, wd = oc.kcenters(x, n_clusters=K + 2, init_centers=init)
+    assert len(wi) == K + 2
+    # the cold start: K distinct frames from default_rng(seed) over all frames
+    # (kmedoids.py:345-352), every frame to its nearest, two sweeps from
+    # RandomState(seed)
+    rng = np.random.default_rng(7)
+    km = np.array([])
+    while len(np.unique(km)) < K:
+        km = rng.integers(0, _EST_N, K)
+    ka, kd = oc.assign_to_nearest_center(x, x[km])
+    rs = np.random.RandomState(7)
+    km = [int(i) for i in km]
+    for _ in range(2):
+        km, kd, ka = oc.pam_update(x, km, ka, kd, random_state=rs)
+    n_occupied = len(np.unique(oc.assign_to_nearest_center(x, init)[0]))
+    assert n_occupied == 3              # (two initial centers attract nothing)
+    for key, want_i, want_a, want_d in (("hy", hy[0], hy[2], hy[1]),
+                                        ("ws", wi, wa, wd), ("km", km, ka, kd)):
+        assert _est_medoids(est_parts, key) == [int(i) for i in want_i], key
+        want_c = x[[int(i) for i in want_i]]
+        if key == "ws":
+            # k-centers alone: the caller's initial centers, then the new ones
+            want_c = np.concatenate([np.array(init), want_c[n_occupied:]])
+        for p in est_parts:
+            np.testing.assert_array_equal(p[key + "_c"], want_c, key)
+            assert p[key + "_c"].dtype == np.float32
+            assert p[key + "_a"].dtype == np.int64
+            assert p[key + "_d"].dtype == np.float64
+        np.testing.assert_array_equal(
+            np.concatenate([p[key + "_a"] for p in est_parts]), want_a, key)
+        np.testing.assert_array_equal(
+            np.concatenate([p[key + "_d"] for p in est_parts]), want_d, key)

@@ -64,6 +64,8 @@ SYMBOLS = [
     "ek_ent_state_counts_close",
     "ek_kmc_create", "ek_kmc_destroy", "ek_kmc_next", "ek_kmc_trajectories",
     "ek_kmc_ensemble", "ek_kmc_fret_probs", "ek_kmc_fret_bursts", "ek_kmc_last_timing",
+    "ek_dye_pair_create", "ek_dye_pair_destroy", "ek_dye_pair_table", "ek_dye_pair_resolve",
+    "ek_dye_pair_static", "ek_dye_pair_last_timing",
     "ek_pockets_open", "ek_pockets_run", "ek_pockets_counts", "ek_pockets_fetch",
     "ek_pockets_last_timing", "ek_pockets_close", "ek_pockets_touches", "ek_pockets_ranks",
     "ek_pockets_labels",
@@ -303,6 +305,15 @@ def load():
     L.ek_kmc_fret_bursts.argtypes = [vp, u64, i64, i64, i64p, i64p, f64p, i64p, f64p, f64p,
                                      C.c_double, C.c_double, i64, u8p, i32p, i64p]
     L.ek_kmc_last_timing.argtypes = [f64p]
+    i8p = C.POINTER(C.c_int8)
+    L.ek_dye_pair_create.argtypes = [C.c_int, i32, i64p, i64p, i32p, f64p, f64p, f64p, i64p,
+                                     i64p, i32p, f64p, f64p, f64p, f64p, C.POINTER(vp)]
+    L.ek_dye_pair_destroy.argtypes = [vp]
+    L.ek_dye_pair_table.argtypes = [vp, i32, f64p, f64p, f64p, f64p]
+    L.ek_dye_pair_resolve.argtypes = [vp, u64, i64, i64, i64, i64, i32p, i8p, i32p, i32p, i64,
+                                      i64p, i64p]
+    L.ek_dye_pair_static.argtypes = [vp, u64, i64, i64, f64p, i8p, i32p, i32p]
+    L.ek_dye_pair_last_timing.argtypes = [f64p]
     L.ek_pockets_open.argtypes = [C.c_int, i32, f64p, C.c_double, i32, C.POINTER(vp)]
     L.ek_pockets_run.argtypes = [vp, f32p, i64, f32p, i32p, i64]
     L.ek_pockets_counts.argtypes = [vp, i64, i64p]
@@ -434,6 +445,10 @@ def i64p(a):
 
 def u8p(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def i8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int8))
 
 
 def u32p(a):

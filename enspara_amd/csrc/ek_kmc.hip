@@ -35,6 +35,7 @@
 // A chain that has to step from a row without nonzeros records the state (integer
 // atomicMin) and stays; the caller raises.
 #include "ek_common.h"
+#include "ek_kmc_dev.h"
 #include "ek_mi_launch.h"
 
 #include <new>
@@ -49,12 +50,6 @@ extern int ek_set_error(int code, const char *fmt, ...);
                                 hipGetErrorString(e_), __FILE__, __LINE__);         \
     } while (0)
 
-#define KMC_TRANS 0u
-#define KMC_INIT 1u
-#define KMC_BIN 2u
-#define KMC_JITTER 3u
-#define KMC_COIN 4u
-
 #define KMC_LANE_WG 64          // lane form, bursts: one wave a workgroup (one LDS tile)
 #define KMC_TS 16               // steps of a tile: 64-byte runs per chain
 #define KMC_WAVE_WG 256         // wave form: four chains a workgroup
@@ -68,91 +63,12 @@ extern int ek_set_error(int code, const char *fmt, ...);
 
 static double kmc_ms[3];        // upload, kernels, download of the last call
 
-struct KmcRows {
-    const int64_t *indptr;
-    const int32_t *cols;
-    const double *cdf;
-    int32_t n;
-};
-
 struct KmcDist {
     const int64_t *off;         // [n_states + 1]
     const double *centres, *cdf;
 };
 
-// ---- uniforms ----------------------------------------------------------------------------
-__device__ __forceinline__ void kmc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                           uint32_t k0, uint32_t k1, uint32_t w[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w[0] = c0;
-    w[1] = c1;
-    w[2] = c2;
-    w[3] = c3;
-}
-
-__device__ __forceinline__ double kmc_double(uint32_t a, uint32_t b)
-{
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
-}
-
-// the two doubles of call i of (stream, chain): indices 2 i and 2 i + 1
-__device__ __forceinline__ void kmc_pair(uint64_t seed, uint32_t stream, uint64_t chain,
-                                         uint64_t i, double &u0, double &u1)
-{
-    uint32_t w[4];
-    kmc_philox((uint32_t)i, (uint32_t)(i >> 32), (uint32_t)chain,
-               (stream << 28) | (uint32_t)(chain >> 32), (uint32_t)seed, (uint32_t)(seed >> 32),
-               w);
-    u0 = kmc_double(w[0], w[1]);
-    u1 = kmc_double(w[2], w[3]);
-}
-
-__device__ __forceinline__ double kmc_uniform(uint64_t seed, uint32_t stream, uint64_t chain,
-                                              uint64_t index)
-{
-    double u0, u1;
-    kmc_pair(seed, stream, chain, index >> 1, u0, u1);
-    return (index & 1) ? u1 : u0;
-}
-
-// ---- the search ----------------------------------------------------------------------------
-// the first k of [lo, hi) with cdf[k] > u; hi - 1 if there is none (hi > lo)
-__device__ __forceinline__ int64_t kmc_upper(const double *__restrict__ cdf, int64_t lo,
-                                             int64_t hi, double u)
-{
-    int64_t a = lo, b = hi - 1;
-    while (a < b) {
-        const int64_t m = (a + b) >> 1;
-        if (cdf[m] > u)
-            b = m;
-        else
-            a = m + 1;
-    }
-    return a;
-}
-
-__device__ __forceinline__ int32_t kmc_step_lane(const KmcRows &R, int32_t s, double u,
-                                                 uint32_t *bad)
-{
-    const int64_t lo = R.indptr[s], hi = R.indptr[s + 1];
-    if (hi <= lo) {
-        atomicMin(bad, (uint32_t)s);
-        return s;
-    }
-    return R.cols[kmc_upper(R.cdf, lo, hi, u)];
-}
-
+// ---- the search (kmc_upper, kmc_step_lane: ek_kmc_dev.h) -------------------------------------
 // s and u are the same in every lane of the wave
 __device__ __forceinline__ int32_t kmc_step_wave(const KmcRows &R, int32_t s, double u, int lane,
                                                  uint32_t *bad)

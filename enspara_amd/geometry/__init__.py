@@ -4,11 +4,15 @@ states (reference enspara/geometry/rotamer.py), Shrake-Rupley solvent-accessible
 surface areas (``sasa``; what the reference takes from mdtraj), LIGSITE pocket
 detection (``pockets``; reference enspara/geometry/pockets.py), smFRET burst
 sampling on a Markov state model (``dyes_from_expt_dist``; the array-only part
-of the reference's module of that name)."""
+of the reference's module of that name), explicit dye geometry and the
+donor-excitation Monte Carlo on dye MSMs (``explicit_r0_calc``, ``dye_lifetimes``;
+reference modules of those names)."""
 from . import libdist  # noqa: F401
 from . import rotamer  # noqa: F401
 from . import sasa  # noqa: F401
 from . import pockets  # noqa: F401
 from . import dyes_from_expt_dist  # noqa: F401
+from . import explicit_r0_calc  # noqa: F401
+from . import dye_lifetimes  # noqa: F401
 from .rotamer import all_rotamers  # noqa: F401
 from .pockets import get_pockets, get_pocket_cells, cluster_pocket_cells  # noqa: F401

@@ -13,9 +13,11 @@ Ported: ``FRET_efficiency``, ``make_distribution``, ``convert_photon_times``,
 Not ported, and why: ``cluster_grids`` (``cluster_grid_points=True`` raises
 ``NotImplementedError``: the reference orders clusters by an ``argsort`` that is
 not stable for ties, so there is nothing exact to hold a port to),
-``rodrigues_rotation`` (and the ``explicit_r0_calc`` and ``dye_lifetimes`` that
-later versions of the reference build on it), and the histogram post-processing (``histogram_to_match_expt``, the moment
-helpers), which is a few numpy lines on the result with nothing to run on a device.
+``rodrigues_rotation``, and the histogram post-processing
+(``histogram_to_match_expt``, the moment helpers), which is a few numpy lines on the
+result with nothing to run on a device.  The explicit treatment of the dyes that later
+versions of the reference build next to this module is ``geometry.explicit_r0_calc`` and
+``geometry.dye_lifetimes``.
 
 There is no topology reader here.  Where the reference takes an mdtraj trajectory
 and residue numbers, these functions take ``xyz`` ([frames, atoms, 3] float32, nm),

@@ -971,6 +971,53 @@ int ek_kmc_fret_bursts(ek_kmc *h, uint64_t seed, int64_t first_burst, int64_t n_
                        int64_t *bad_out);
 int ek_kmc_last_timing(double *ms_out);
 
+/* ---- donor-excitation Monte Carlo on a pair of dye MSMs -------------------------------
+ * Replaces enspara/geometry/dye_lifetimes.py (resolve_excitation, explicit_static_dyes,
+ * fully_averaged_explict_dyes) and the pair arithmetic of explicit_r0_calc.py
+ * (csrc/ek_dye_pair.hip).  All arrays are host memory.
+ * A handle holds n_problems problems side by side.  Per side (d_: donors, a_: acceptors):
+ * off [n_problems + 1] = the first state of every problem in the side's one numbering, a
+ * state at least per problem; indptr [n + 1], cols [nnz], cdf [nnz] = the rows of all
+ * problems compressed as for ek_kmc_create, cols in the side's numbering and within the
+ * row's problem (EK_EARG otherwise); init [n] = per problem cumsum(eq probs) / its last;
+ * xyz [n][9] = emission centre, dipole origin, dipole vector.  consts [n_problems][6] =
+ * p_rad, p_nonrad, dt, c6, 1 / Td, 0 with R0^6 = c6 k2.
+ * Uniforms as for ek_kmc; streams 5 decay (index = the step), 6 donor and 7 acceptor
+ * (index 0: the initial state, t + 1: the hop of step t), 8 the FRET coin (index 0).
+ * Sample j of problem p is chain first_chain + p 2^32 + j; 1 <= n_samples < 2^32,
+ * n_problems * n_samples < 2^31, first_chain < 2^59.
+ * ek_dye_pair_table: k2, r, FE [nd][na] and the decay cdf [nd][na][3] of one problem.
+ * ek_dye_pair_resolve, dtraj_out null: steps [n_problems][n_samples] (out) and
+ * outcomes_out (0 radiative, 1 non-radiative, 2 energy transfer; 3: still excited after
+ * max_steps) of every sample.  step_cap: steps per launch, max_steps: steps per
+ * excitation (0: the defaults; max_steps < 2^24); neither changes a result.  over_out: -1,
+ * or the first sample still excited after max_steps.  bad_out [2]: -1, or the smallest
+ * donor / acceptor state (the side's numbering) with an empty row that had to hop.
+ * dtraj_out, atraj_out not null: steps is input (what the first form returned); the
+ * states of sample after sample, steps + 1 each, in the problem's own numbering;
+ * traj_cells = sum(steps + 1) (EK_EARG otherwise).
+ * ek_dye_pair_static: acceptor_out[i] = 1 iff the coin of sample i <= FE of its chain's
+ * initial states (dstate_out, astate_out), or <= fe_fixed[problem] where fe_fixed is given.
+ * ek_dye_pair_last_timing: ms_out[3] = upload, kernels, download of the last call. */
+typedef struct ek_dye_pair ek_dye_pair;
+int ek_dye_pair_create(int device, int32_t n_problems, const int64_t *d_off,
+                       const int64_t *d_indptr, const int32_t *d_cols, const double *d_cdf,
+                       const double *d_init, const double *d_xyz, const int64_t *a_off,
+                       const int64_t *a_indptr, const int32_t *a_cols, const double *a_cdf,
+                       const double *a_init, const double *a_xyz, const double *consts,
+                       ek_dye_pair **out);
+int ek_dye_pair_destroy(ek_dye_pair *h);
+int ek_dye_pair_table(ek_dye_pair *h, int32_t problem, double *k2_out, double *r_out,
+                      double *fe_out, double *cdf_out);
+int ek_dye_pair_resolve(ek_dye_pair *h, uint64_t seed, int64_t first_chain, int64_t n_samples,
+                        int64_t step_cap, int64_t max_steps, int32_t *steps,
+                        int8_t *outcomes_out, int32_t *dtraj_out, int32_t *atraj_out,
+                        int64_t traj_cells, int64_t *bad_out, int64_t *over_out);
+int ek_dye_pair_static(ek_dye_pair *h, uint64_t seed, int64_t first_chain, int64_t n_samples,
+                       const double *fe_fixed, int8_t *acceptor_out, int32_t *dstate_out,
+                       int32_t *astate_out);
+int ek_dye_pair_last_timing(double *ms_out);
+
 /* ---- dihedral angles and buffered rotamer states ------------------------------------
  * Replaces enspara/geometry/rotamer.py (csrc/ek_rotamer.hip).  All arrays are host
  * memory.  A dihedral is of one of n_kinds kinds (kind [n] bytes); kind k has

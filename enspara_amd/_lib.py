@@ -66,6 +66,8 @@ SYMBOLS = [
     "ek_kmc_ensemble", "ek_kmc_fret_probs", "ek_kmc_fret_bursts", "ek_kmc_last_timing",
     "ek_dye_pair_create", "ek_dye_pair_destroy", "ek_dye_pair_table", "ek_dye_pair_resolve",
     "ek_dye_pair_static", "ek_dye_pair_last_timing",
+    "ek_dye_bursts_lifetimes", "ek_dye_bursts_k2", "ek_dye_photons_lifetimes",
+    "ek_dye_photons_k2", "ek_dye_pick_events", "ek_dye_bursts_last_timing",
     "ek_pockets_open", "ek_pockets_run", "ek_pockets_counts", "ek_pockets_fetch",
     "ek_pockets_last_timing", "ek_pockets_close", "ek_pockets_touches", "ek_pockets_ranks",
     "ek_pockets_labels",
@@ -314,6 +316,17 @@ def load():
                                       i64p, i64p]
     L.ek_dye_pair_static.argtypes = [vp, u64, i64, i64, f64p, i8p, i32p, i32p]
     L.ek_dye_pair_last_timing.argtypes = [f64p]
+    L.ek_dye_bursts_lifetimes.argtypes = [vp, u64, i64, i64, i64p, i64p, f64p, i64p, f64p, u8p,
+                                          i64, u8p, f64p, i32p, i32p, i64p, i64p]
+    L.ek_dye_bursts_k2.argtypes = [vp, u64, i64, i64, i64p, i64p, f64p, i64p, f64p, i64p, f64p,
+                                   C.c_double, i64, u8p, f64p, f64p, i32p, i32p, i32p, i32p,
+                                   i64p, i64p]
+    L.ek_dye_photons_lifetimes.argtypes = [C.c_int, u64, i64, i64, i32p, i32, i64p, f64p, u8p,
+                                           u8p, f64p, i64p]
+    L.ek_dye_photons_k2.argtypes = [C.c_int, u64, i64, i64, i32p, i32, i64p, f64p, i64p, f64p,
+                                    C.c_double, u8p, f64p, f64p, i32p, i32p, i64p]
+    L.ek_dye_pick_events.argtypes = [C.c_int, i64, i32p, f64p, i32, i64p, i64p, i64p]
+    L.ek_dye_bursts_last_timing.argtypes = [f64p]
     L.ek_pockets_open.argtypes = [C.c_int, i32, f64p, C.c_double, i32, C.POINTER(vp)]
     L.ek_pockets_run.argtypes = [vp, f32p, i64, f32p, i32p, i64]
     L.ek_pockets_counts.argtypes = [vp, i64, i64p]

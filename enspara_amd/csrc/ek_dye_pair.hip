@@ -10,7 +10,8 @@
 //   off[p] .. off[p + 1]), their compressed rows (indptr, cols in that numbering, cdf), the
 //   initial-state cdf and 9 doubles a state (emission centre, dipole origin, dipole vector);
 //   per problem the constants K = {p_rad, p_nonrad, dt, c6, 1 / Td, 0} made by the host.
-// A pair (dp_pair, the one function every kernel calls).  r2 = |centre_D - centre_A|^2, r =
+// A pair (dp_pair, the one function every kernel calls; its geometry up to FE is dp_geom of
+//   ek_dye_geom.h, which ek_dye_bursts.hip calls too).  r2 = |centre_D - centre_A|^2, r =
 //   sqrt(r2); rvec = origin_D - origin_A; cosT = A.D / (|A| |D|), cosD = rvec.D / (|rvec| |D|),
 //   cosA = A.rvec / (|A| |rvec|); k2 = (cosT - 3 cosD cosA)^2; R0^6 = c6 k2; r6 = r2 r2 r2;
 //   FE = R0^6 / (R0^6 + r6); kRET = (1 / Td) R0^6 / r6; p_RET = 1 - exp(-kRET dt); p = {p_rad,
@@ -32,6 +33,7 @@
 // A side that has to hop from a row without nonzeros records the state (integer atomicMin)
 // and stays; the caller raises.  No float atomics.
 #include "ek_common.h"
+#include "ek_dye_geom.h"
 #include "ek_kmc_dev.h"
 #include "ek_mi_launch.h"
 
@@ -78,32 +80,16 @@ struct DpPair {
 };
 
 // ---- the pair ------------------------------------------------------------------------------
-__device__ __forceinline__ double dp_dot(double ax, double ay, double az, double bx, double by,
-                                         double bz)
-{
-    return ax * bx + ay * by + az * bz;
-}
-
 __device__ __forceinline__ void dp_pair(const double *__restrict__ d, const double *__restrict__ a,
                                         double p_rad, double p_nonrad, double dt, double c6,
                                         double inv_td, DpPair &q)
 {
-    const double cx = d[0] - a[0], cy = d[1] - a[1], cz = d[2] - a[2];
-    const double r2 = dp_dot(cx, cy, cz, cx, cy, cz);
-    const double vx = d[3] - a[3], vy = d[4] - a[4], vz = d[5] - a[5];
-    const double Dx = d[6], Dy = d[7], Dz = d[8], Ax = a[6], Ay = a[7], Az = a[8];
-    const double nD = sqrt(dp_dot(Dx, Dy, Dz, Dx, Dy, Dz));
-    const double nA = sqrt(dp_dot(Ax, Ay, Az, Ax, Ay, Az));
-    const double nR = sqrt(dp_dot(vx, vy, vz, vx, vy, vz));
-    const double cosT = dp_dot(Ax, Ay, Az, Dx, Dy, Dz) / (nA * nD);
-    const double cosD = dp_dot(vx, vy, vz, Dx, Dy, Dz) / (nR * nD);
-    const double cosA = dp_dot(Ax, Ay, Az, vx, vy, vz) / (nA * nR);
-    const double k = cosT - 3.0 * cosD * cosA;
-    q.k2 = k * k;
-    q.r = sqrt(r2);
-    const double r06 = c6 * q.k2;
-    const double r6 = r2 * r2 * r2;
-    q.FE = r06 / (r06 + r6);
+    DpGeom g;
+    dp_geom(d, a, c6, g);       // (ek_dye_geom.h)
+    q.k2 = g.k2;
+    q.r = g.r;
+    q.FE = g.FE;
+    const double r06 = g.r06, r6 = g.r6;
     const double kret = inv_td * r06 / r6;
     const double p_ret = 1.0 - exp(-kret * dt);
     double p0 = p_rad, p1 = p_nonrad, p2 = p_ret, p3 = 1.0 - p_rad - p_nonrad - p_ret;

@@ -31,35 +31,18 @@
 // Bursts.  A lane per burst: the chain starts at the inverse CDF of the populations, runs
 //   to the burst's last frame and serves its photons on the way: bin by inverse CDF of the
 //   state's histogram, d = centre + (u * bin_width - bin_width / 2), d2 = d * d, d6 = d2 *
-//   d2 * d2, E = r06 / (r06 + d6), acceptor iff coin <= E.  One byte per photon.
+//   d2 * d2, E = r06 / (r06 + d6), acceptor iff coin <= E.  One byte per photon.  The chain loop
+//   and the host side of a call are ek_kmc_burst.h's, shared with the explicit-dye rules of
+//   ek_dye_bursts.hip; this file has the histogram rule (KmcHistRule).
 // A chain that has to step from a row without nonzeros records the state (integer
 // atomicMin) and stays; the caller raises.
-#include "ek_common.h"
-#include "ek_kmc_dev.h"
-#include "ek_mi_launch.h"
+#include "ek_kmc_burst.h"
 
-#include <new>
-
-extern int ek_set_error(int code, const char *fmt, ...);
-
-#define KMC_HIP(call)                                                               \
-    do {                                                                            \
-        hipError_t e_ = (call);                                                     \
-        if (e_ != hipSuccess)                                                       \
-            return ek_set_error(EK_EHIP, "%s failed: %s at %s:%d", #call,           \
-                                hipGetErrorString(e_), __FILE__, __LINE__);         \
-    } while (0)
-
-#define KMC_LANE_WG 64          // lane form, bursts: one wave a workgroup (one LDS tile)
-#define KMC_TS 16               // steps of a tile: 64-byte runs per chain
 #define KMC_WAVE_WG 256         // wave form: four chains a workgroup
-#define KMC_WG 256
-#define KMC_STEP_CAP 16384      // steps of a launch unless the caller says otherwise
 #define KMC_BUF_BYTES ((int64_t)256 << 20)  // the trajectories' device buffer
 #define KMC_MIN_CHUNK 1024      // steps of a buffer at least, before the chains are split
 #define KMC_WAVE_MAX_CHAINS 2048    // form 0: up to this many chains take a wave each
 #define KMC_ENS_ROWS 64
-#define KMC_NO_BAD 0xffffffffu
 
 static double kmc_ms[3];        // upload, kernels, download of the last call
 
@@ -95,21 +78,6 @@ __device__ __forceinline__ int32_t kmc_step_wave(const KmcRows &R, int32_t s, do
     const unsigned long long mask = __ballot(pred);
     const int64_t k = mask ? (int64_t)(__ffsll(mask) - 1) : len - 1;
     return R.cols[lo + k];
-}
-
-// tile [64 chains][KMC_TS steps] of one wave -> out: chain c's cnt steps go to out[off ..],
-// four chains (64 bytes each) per store instruction.  off, cnt: this lane's chain's.
-__device__ __forceinline__ void kmc_tile_flush(const int32_t (*tile)[KMC_TS + 1], int lane,
-                                               long long off, int cnt, int32_t *__restrict__ out)
-{
-#pragma unroll 4
-    for (int i = 0; i < EK_WAVE / 4; ++i) {
-        const int c = i * 4 + (lane >> 4), j = lane & (KMC_TS - 1);
-        const long long offc = __shfl(off, c, EK_WAVE);
-        const int cntc = __shfl(cnt, c, EK_WAVE);
-        if (j < cntc)
-            out[offc + j] = tile[c][j];
-    }
 }
 
 // ---- chains --------------------------------------------------------------------------------
@@ -216,72 +184,20 @@ kmc_fret_probs_kernel(KmcDist D, int32_t n_states, uint64_t seed, uint64_t chain
                         kmc_uniform(seed, KMC_JITTER, chain, (uint64_t)k), bw, r06);
 }
 
-// frames t0 .. t0 + m - 1 of every burst that reaches them.  cur: the state at frame t0
-// (t0 > 0), kpos: the first photon not yet served.  traj (may be null): flat, burst b's
-// states from toff[b].
-__global__ void __launch_bounds__(KMC_LANE_WG)
-kmc_burst_kernel(KmcRows R, KmcDist D, uint64_t seed, int64_t first_burst, int64_t n_bursts,
-                 const int64_t *__restrict__ foff, const int64_t *__restrict__ frames,
-                 const double *__restrict__ pop_cdf, double bw, double r06,
-                 int32_t *__restrict__ cur, int64_t *__restrict__ kpos, int64_t t0, int64_t m,
-                 uint8_t *__restrict__ photons, int32_t *__restrict__ traj,
-                 const int64_t *__restrict__ toff, uint32_t *__restrict__ bad)
-{
-    __shared__ int32_t tile[EK_WAVE][KMC_TS + 1];
-    const int lane = threadIdx.x;
-    const int64_t b = (int64_t)blockIdx.x * KMC_LANE_WG + lane;
-    const bool live = b < n_bursts;
-    const uint64_t chain = (uint64_t)(first_burst + b);
-    int64_t k0 = 0, k1 = 0, last = -1, k = 0, tbase = 0;
-    int32_t s = 0;
-    if (live) {
-        k0 = foff[b];
-        k1 = foff[b + 1];
-        last = frames[k1 - 1];
-        if (traj)
-            tbase = toff[b];
-        if (t0 == 0) {
-            s = (int32_t)kmc_upper(pop_cdf, 0, R.n, kmc_uniform(seed, KMC_INIT, chain, 0));
-            k = k0;
-        } else if (t0 <= last) {
-            s = cur[b];
-            k = kpos[b];
-        }
+// the histogram rule of the burst loop (ek_kmc_burst.h): a distance from the state's histogram,
+// its efficiency, a coin
+struct KmcHistRule {
+    KmcDist D;
+    uint64_t seed;
+    double bw, r06;
+    uint8_t *photons;
+    __device__ __forceinline__ void photon(int32_t s, uint64_t chain, uint64_t ph, int64_t k) const
+    {
+        const double E = kmc_photon_E(D, s, kmc_uniform(seed, KMC_BIN, chain, ph),
+                                      kmc_uniform(seed, KMC_JITTER, chain, ph), bw, r06);
+        photons[k] = kmc_uniform(seed, KMC_COIN, chain, ph) <= E ? 1 : 0;
     }
-    const int64_t tend = last < t0 + m - 1 ? last : t0 + m - 1;    // the last frame done here
-    double u0 = 0.0, u1 = 0.0;
-    bool first = true;
-    for (int64_t tb = t0; __any(tb <= tend); tb += KMC_TS) {
-        const int64_t left = tend - tb + 1;
-        const int cnt = (int)(left < 0 ? 0 : left < KMC_TS ? left : KMC_TS);
-        for (int j = 0; j < cnt; ++j) {
-            const int64_t t = tb + j;
-            tile[lane][j] = s;
-            while (k < k1 && frames[k] == t) {
-                const uint64_t ph = (uint64_t)(k - k0);
-                const double E = kmc_photon_E(D, s, kmc_uniform(seed, KMC_BIN, chain, ph),
-                                              kmc_uniform(seed, KMC_JITTER, chain, ph), bw, r06);
-                photons[k] = kmc_uniform(seed, KMC_COIN, chain, ph) <= E ? 1 : 0;
-                ++k;
-            }
-            if (t < last) {
-                if (!(t & 1) || first)
-                    kmc_pair(seed, KMC_TRANS, chain, (uint64_t)t >> 1, u0, u1);
-                first = false;
-                s = kmc_step_lane(R, s, (t & 1) ? u1 : u0, bad);
-            }
-        }
-        if (traj) {             // (the same in every lane)
-            __syncthreads();
-            kmc_tile_flush(tile, lane, (long long)(tbase + tb), cnt, traj);
-            __syncthreads();
-        }
-    }
-    if (live && t0 + m - 1 < last) {
-        cur[b] = s;
-        kpos[b] = k;
-    }
-}
+};
 
 // ---- ensemble ------------------------------------------------------------------------------
 __global__ void __launch_bounds__(KMC_WG)
@@ -348,79 +264,6 @@ kmc_ens_dot_kernel(const double *__restrict__ p, const double *__restrict__ o, i
 }
 
 // ---- host ----------------------------------------------------------------------------------
-// what a call allocated, released whichever way the call returns
-struct KmcScope {
-    void *ptr[24];
-    int n = 0;
-    hipStream_t sync = nullptr;     // not owned: waited for before anything is freed
-    hipStream_t own = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    template <class T> hipError_t alloc(T **p, size_t bytes)
-    {
-        if (n >= 24)
-            return hipErrorOutOfMemory;
-        hipError_t e = ek_dev_malloc((void **)p, bytes ? bytes : 1);
-        if (e == hipSuccess)
-            ptr[n++] = (void *)*p;
-        return e;
-    }
-    hipError_t events()
-    {
-        for (hipEvent_t &e : ev) {
-            hipError_t r = ek_event_create(&e);
-            if (r != hipSuccess)
-                return r;
-        }
-        return hipSuccess;
-    }
-    ~KmcScope()
-    {
-        if (sync)
-            (void)hipStreamSynchronize(sync);
-        if (own)
-            (void)hipStreamSynchronize(own);
-        for (int i = 0; i < n; ++i)
-            (void)ek_dev_free(ptr[i]);
-        for (hipEvent_t e : ev)
-            if (e)
-                (void)ek_event_destroy(e);
-        if (own)
-            (void)ek_stream_destroy(own);
-    }
-};
-
-struct ek_kmc {
-    int device;
-    int32_t n;
-    int64_t nnz;
-    int64_t *d_indptr;
-    int32_t *d_cols;
-    double *d_cdf;
-    hipStream_t s;
-};
-
-static KmcRows kmc_rows(const ek_kmc *h)
-{
-    KmcRows R;
-    R.indptr = h->d_indptr;
-    R.cols = h->d_cols;
-    R.cdf = h->d_cdf;
-    R.n = h->n;
-    return R;
-}
-
-static int kmc_set_device(int device)
-{
-    hipError_t e0 = hipSetDevice(device);
-    if (e0 != hipSuccess)
-        return ek_set_error(EK_EHIP, "hipSetDevice(%d): %s", device, hipGetErrorString(e0));
-    return EK_OK;
-}
-
-static unsigned kmc_blocks(int64_t items, int per) { return (unsigned)((items + per - 1) / per); }
-
-static int64_t kmc_bad(uint32_t w) { return w == KMC_NO_BAD ? (int64_t)-1 : (int64_t)w; }
-
 extern "C" int ek_kmc_create(int device, int32_t n_states, const int64_t *indptr,
                              const int32_t *cols, const double *cdf, ek_kmc **out)
 {
@@ -495,16 +338,6 @@ extern "C" int ek_kmc_destroy(ek_kmc *h)
     return EK_OK;
 }
 
-static int kmc_store_ms(KmcScope &sc)
-{
-    float ms = 0.f;
-    for (int q = 0; q < 3; ++q) {
-        KMC_HIP(hipEventElapsedTime(&ms, sc.ev[q], sc.ev[q + 1]));
-        kmc_ms[q] = ms;
-    }
-    return EK_OK;
-}
-
 extern "C" int ek_kmc_next(ek_kmc *h, int64_t n, const int32_t *states, const double *u,
                            int32_t *next_out, int64_t *bad_out)
 {
@@ -539,7 +372,7 @@ extern "C" int ek_kmc_next(ek_kmc *h, int64_t n, const int32_t *states, const do
     KMC_HIP(hipEventRecord(sc.ev[3], h->s));
     KMC_HIP(hipStreamSynchronize(h->s));
     *bad_out = kmc_bad(bad);
-    return kmc_store_ms(sc);
+    return kmc_store_ms(sc, kmc_ms);
 }
 
 extern "C" int ek_kmc_trajectories(ek_kmc *h, uint64_t seed, int64_t first_chain,
@@ -744,7 +577,7 @@ extern "C" int ek_kmc_ensemble(int device, int32_t n, const double *T, const int
     }
     KMC_HIP(hipEventRecord(sc.ev[3], s));
     KMC_HIP(hipStreamSynchronize(s));
-    return kmc_store_ms(sc);
+    return kmc_store_ms(sc, kmc_ms);
 }
 
 // ---- photons -------------------------------------------------------------------------------
@@ -820,8 +653,30 @@ extern "C" int ek_kmc_fret_probs(int device, uint64_t seed, int64_t chain, int64
     KMC_HIP(hipMemcpyAsync(E_out, d_E, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     KMC_HIP(hipEventRecord(sc.ev[3], s));
     KMC_HIP(hipStreamSynchronize(s));
-    return kmc_store_ms(sc);
+    return kmc_store_ms(sc, kmc_ms);
 }
+
+// the histogram rule's host side (kmc_run_bursts)
+struct KmcHistPlan {
+    int32_t n_states;
+    const int64_t *dist_off;
+    const double *centres, *dist_cdf;
+    double bw, r06;
+    KmcDist D;
+    size_t bytes(int64_t) const
+    {
+        return (size_t)(n_states + 1) * 8 + (size_t)dist_off[n_states] * 16;
+    }
+    int upload(KmcScope &sc, hipStream_t s, int64_t)
+    {
+        return kmc_upload_dist(sc, s, n_states, dist_off, centres, dist_cdf, &D);
+    }
+    KmcHistRule rule(uint64_t seed, uint8_t *d_flags, uint32_t *) const
+    {
+        return KmcHistRule{D, seed, bw, r06, d_flags};
+    }
+    int download(hipStream_t, int64_t) { return EK_OK; }
+};
 
 extern "C" int ek_kmc_fret_bursts(ek_kmc *h, uint64_t seed, int64_t first_burst,
                                   int64_t n_bursts, const int64_t *frame_off,
@@ -832,105 +687,14 @@ extern "C" int ek_kmc_fret_bursts(ek_kmc *h, uint64_t seed, int64_t first_burst,
                                   int64_t *bad_out)
 {
     int rc = EK_OK;
-    if (!h || !frame_off || !frames || !pop_cdf || !photons_out || !bad_out || n_bursts < 1 ||
-        n_bursts > ((int64_t)1 << 31) || first_burst < 0 || step_cap < 0 ||
-        first_burst > ((int64_t)1 << 60) - n_bursts || frame_off[0] != 0)
-        return ek_set_error(EK_EARG, "ek_kmc_fret_bursts: bad argument (1 <= n_bursts <= 2^31, "
-                                     "chains below 2^60, frame_off[0] == 0, step_cap >= 0)");
+    if (!h)
+        return ek_set_error(EK_EARG, "ek_kmc_fret_bursts: null argument");
     if ((rc = kmc_check_dist(h->n, dist_off, centres, dist_cdf, "ek_kmc_fret_bursts")) != EK_OK)
         return rc;
-    int64_t max_last = 0, traj_cells = 0;
-    for (int64_t b = 0; b < n_bursts; ++b) {
-        if (frame_off[b + 1] <= frame_off[b])
-            return ek_set_error(EK_EARG, "ek_kmc_fret_bursts: burst %lld has no photon",
-                                (long long)b);
-        int64_t prev = 0;
-        for (int64_t k = frame_off[b]; k < frame_off[b + 1]; ++k) {
-            if (frames[k] < prev || frames[k] >= ((int64_t)1 << 40))
-                return ek_set_error(EK_EARG, "ek_kmc_fret_bursts: the frames of burst %lld are "
-                                             "negative, decrease or exceed 2^40", (long long)b);
-            prev = frames[k];
-        }
-        max_last = prev > max_last ? prev : max_last;
-        traj_cells += prev + 1;
-    }
-    *bad_out = -1;
-    if ((rc = kmc_set_device(h->device)) != EK_OK)
-        return rc;
-    const int64_t n_ph = frame_off[n_bursts];
-    const size_t tb = traj_out ? (size_t)traj_cells * sizeof(int32_t) + (size_t)(n_bursts + 1) * 8
-                               : 0;
-    if ((rc = ek_mi_check_memory(tb + (size_t)n_ph * 9 + (size_t)n_bursts * 20 +
-                                 (size_t)h->n * 16 + (size_t)dist_off[h->n] * 16 + 1024,
-                                 "ek_kmc_fret_bursts")) != EK_OK)
-        return rc;
-    const int64_t cap = step_cap > 0 ? step_cap : KMC_STEP_CAP;
-    KmcScope sc;
-    sc.sync = h->s;
-    hipStream_t s = h->s;
-    KmcDist D;
-    int64_t *d_foff = nullptr, *d_frames = nullptr, *d_kpos = nullptr, *d_toff = nullptr;
-    double *d_pop = nullptr;
-    int32_t *d_cur = nullptr, *d_traj = nullptr;
-    uint8_t *d_ph = nullptr;
-    uint32_t *d_bad = nullptr, bad = KMC_NO_BAD;
-    int64_t *toff = nullptr;
-    KMC_HIP(sc.events());
-    KMC_HIP(sc.alloc(&d_foff, (size_t)(n_bursts + 1) * sizeof(int64_t)));
-    KMC_HIP(sc.alloc(&d_frames, (size_t)n_ph * sizeof(int64_t)));
-    KMC_HIP(sc.alloc(&d_kpos, (size_t)n_bursts * sizeof(int64_t)));
-    KMC_HIP(sc.alloc(&d_cur, (size_t)n_bursts * sizeof(int32_t)));
-    KMC_HIP(sc.alloc(&d_pop, (size_t)h->n * sizeof(double)));
-    KMC_HIP(sc.alloc(&d_ph, (size_t)n_ph));
-    KMC_HIP(sc.alloc(&d_bad, sizeof(uint32_t)));
-    if (traj_out) {
-        KMC_HIP(sc.alloc(&d_traj, (size_t)traj_cells * sizeof(int32_t)));
-        KMC_HIP(sc.alloc(&d_toff, (size_t)(n_bursts + 1) * sizeof(int64_t)));
-        toff = new (std::nothrow) int64_t[n_bursts + 1];
-        if (!toff)
-            return ek_set_error(EK_ENOMEM, "ek_kmc_fret_bursts: out of host memory");
-        toff[0] = 0;
-        for (int64_t b = 0; b < n_bursts; ++b)
-            toff[b + 1] = toff[b] + frames[frame_off[b + 1] - 1] + 1;
-    }
-    rc = [&]() -> int {
-        KMC_HIP(hipEventRecord(sc.ev[0], s));
-        int rc2 = kmc_upload_dist(sc, s, h->n, dist_off, centres, dist_cdf, &D);
-        if (rc2 != EK_OK)
-            return rc2;
-        KMC_HIP(hipMemcpyAsync(d_foff, frame_off, (size_t)(n_bursts + 1) * sizeof(int64_t),
-                               hipMemcpyHostToDevice, s));
-        KMC_HIP(hipMemcpyAsync(d_frames, frames, (size_t)n_ph * sizeof(int64_t),
-                               hipMemcpyHostToDevice, s));
-        KMC_HIP(hipMemcpyAsync(d_pop, pop_cdf, (size_t)h->n * sizeof(double),
-                               hipMemcpyHostToDevice, s));
-        if (traj_out)
-            KMC_HIP(hipMemcpyAsync(d_toff, toff, (size_t)(n_bursts + 1) * sizeof(int64_t),
-                                   hipMemcpyHostToDevice, s));
-        KMC_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(uint32_t), s));
-        KMC_HIP(hipStreamSynchronize(s));      // (toff is released when this returns)
-        KMC_HIP(hipEventRecord(sc.ev[1], s));
-        for (int64_t t0 = 0; t0 <= max_last; t0 += cap) {
-            hipLaunchKernelGGL(kmc_burst_kernel, dim3(kmc_blocks(n_bursts, KMC_LANE_WG)),
-                               dim3(KMC_LANE_WG), 0, s, kmc_rows(h), D, seed, first_burst,
-                               n_bursts, d_foff, d_frames, d_pop, bin_width, r06, d_cur, d_kpos,
-                               t0, cap, d_ph, d_traj, d_toff, d_bad);
-            KMC_HIP(hipGetLastError());
-        }
-        KMC_HIP(hipEventRecord(sc.ev[2], s));
-        KMC_HIP(hipMemcpyAsync(photons_out, d_ph, (size_t)n_ph, hipMemcpyDeviceToHost, s));
-        if (traj_out)
-            KMC_HIP(hipMemcpyAsync(traj_out, d_traj, (size_t)traj_cells * sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, s));
-        KMC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        KMC_HIP(hipEventRecord(sc.ev[3], s));
-        KMC_HIP(hipStreamSynchronize(s));
-        return kmc_store_ms(sc);
-    }();
-    delete[] toff;
-    if (rc == EK_OK)
-        *bad_out = kmc_bad(bad);
-    return rc;
+    KmcHistPlan plan{h->n, dist_off, centres, dist_cdf, bin_width, r06, KmcDist()};
+    return kmc_run_bursts(h, "ek_kmc_fret_bursts", kmc_ms, seed, first_burst, n_bursts,
+                          frame_off, frames, pop_cdf, step_cap, photons_out, traj_out, bad_out,
+                          nullptr, plan);
 }
 
 extern "C" int ek_kmc_last_timing(double *ms_out)

@@ -1,5 +1,6 @@
 // ek_kmc_dev.h -- what the samplers share on the device: the Philox doubles, the compressed
-// rows and the search of a row's cdf (ek_kmc.hip, ek_dye_pair.hip).
+// rows and the search of a row's cdf (ek_kmc.hip, ek_dye_pair.hip, ek_dye_bursts.hip; DESIGN.md
+// 4k, 4m, 4n).
 //
 // Uniforms.  Philox4x32-10, key = the 64-bit seed (low word first), counter = {i lo, i hi,
 //   chain lo, stream << 28 | chain hi} with i = index >> 1: one call serves the indices
@@ -18,6 +19,11 @@
 #define KMC_DONOR 6u            // index 0: the initial state, t + 1: the hop of step t
 #define KMC_ACCEPTOR 7u
 #define KMC_FRET_COIN 8u        // index 0: the coin of the static and isotropic treatments
+// ek_dye_bursts.hip: the photons of a burst with explicit dyes (index = the photon within its
+// burst; the coin of the kappa-squared rule is KMC_COIN).  12 .. 15 are free.
+#define KMC_EVENT 9u            // the entry of the state's photon events
+#define KMC_DCONF 10u           // the donor's conformation
+#define KMC_ACONF 11u           // the acceptor's
 
 struct KmcRows {
     const int64_t *indptr;

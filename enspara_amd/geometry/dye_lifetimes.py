@@ -48,29 +48,61 @@ Where this differs from the reference, on purpose:
   device call; a dye that has to hop from a state whose row is empty, or an
   excitation still excited after ``max_steps`` steps, raises ``DataInvalid``.
 
+Bursts (csrc/ek_dye_bursts.hip).  ``calc_lifetimes_many`` gives a table of
+``(lifetimes, outcomes)`` per protein state; ``sample_lifetime_bursts`` resamples it on
+the protein MSM's time scale: a burst is a chain of the protein MSM (burst ``b`` is
+chain ``b`` of the seed, exactly the chain of
+``dyes_from_expt_dist.sample_FRET_histograms`` and of
+``explicit_r0_calc.simulate_burst_k2``), and photon ``k`` of it draws one of the photon
+events of the state the chain is in, with double ``k`` of the chain's event stream:
+entry ``min(m - 1, int(u m))`` of the ``m`` photon events (``event_table``).
+``sample_lifetimes_guarenteed_photon`` is one such burst,
+``_sample_lifetimes_guarenteed_photon`` the draw alone on a list of states,
+``extract_fret_efficiency_lifetimes`` and ``remake_prot_MSM_from_lifetimes`` the
+reference's host steps, ``run_mc`` their composition (the reference's ``remake_msms``
+is its first step).  On purpose different from the reference here:
+
+* *seeding and chains*: one seed reproduces a run and every burst has its own chain; the
+  reference seeds only the initial state and lets ``synthetic_trajectory`` and the
+  event draws use other generators;
+* *the rejection loop becomes one draw*: drawing uniformly among all events and
+  redrawing the non-radiative ones is the same distribution as one uniform draw among
+  the photon events, so the loop is gone; a state without a photon event (dyeless, or
+  with non-radiative events only) raises ``DataInvalid`` naming it, where the
+  reference fails or spins forever;
+* ``remake_prot_MSM_from_lifetimes`` and ``run_mc`` take arrays and return arrays:
+  messages go to ``logging``, no file is read or written, and a removed state's
+  equilibrium probability is exactly 0, as in ``make_dye_msm``.
+
 Not ported: ``load_dye``, ``load_library``, ``get_dye_overlap`` (files, yaml, pandas);
 ``align_full_dye_to_res``, ``remove_touches_protein_dye_traj`` (mdtraj: the caller
 passes aligned coordinates and ``keep``; the touch test itself is
-``dyes_from_expt_dist.remove_touches_protein``);
-``sample_lifetimes_guarenteed_photon``, ``run_mc``, ``remake_msms`` and
-``simulate_burst_k2`` (burst-level resampling on top of this); the ``curve_fit``
-helpers (scipy on the host); the ``save_*`` file outputs.
+``dyes_from_expt_dist.remove_touches_protein``); the ``curve_fit`` helpers (scipy on
+the host); the ``save_*`` file outputs.
 """
 import collections
 import ctypes
+import logging
 
 import numpy as np
 
 from .. import _lib, exception, ra
 from ..msm import builders
 from ..msm import synthetic_data as sd
+from . import dyes_from_expt_dist as dyes
 from . import explicit_r0_calc as r0c
 
 __all__ = ["FRET_rate", "calc_dye_radiative_rates", "calc_energy_transfer_prob",
            "calc_per_state_FE", "make_dye_msm", "OUTCOMES", "outcome_names", "problem",
            "geometry_problem", "DyePair", "resolve_excitations", "explicit_static_dyes",
            "fully_averaged_explicit_dyes", "calc_lifetimes", "calc_lifetimes_many",
-           "last_seed", "last_timing", "CHUNK_BYTES", "MAX_STEPS"]
+           "last_seed", "last_timing", "CHUNK_BYTES", "MAX_STEPS", "EventTable", "event_table",
+           "sample_lifetime_bursts", "sample_lifetimes_guarenteed_photon",
+           "_sample_lifetimes_guarenteed_photon", "pick_events",
+           "extract_fret_efficiency_lifetimes", "remake_prot_MSM_from_lifetimes", "run_mc",
+           "last_burst_timing", "burst_timing"]
+
+_log = logging.getLogger(__name__)
 
 OUTCOMES = ("radiative", "non_radiative", "energy_transfer")
 #: device bytes of one call's problems and samples, above which a list is cut
@@ -634,3 +666,371 @@ def last_timing():
     ms = np.zeros(3)
     _lib.check(_lib.load().ek_dye_pair_last_timing(_lib.f64p(ms)))
     return ms
+
+
+# ---- bursts on the protein MSM (csrc/ek_dye_bursts.hip) ------------------------
+EventTable = collections.namedtuple("EventTable", ["off", "life", "flag", "counts", "n_events"])
+_CODE_OF = {name: k for k, name in enumerate(OUTCOMES)}
+_MAX_PICK = 2 ** 31 - 1       # entries of a state's list: pick(u, m) takes m < 2^31
+
+
+def _outcome_codes(outcomes, state):
+    o = np.asarray(outcomes)
+    if o.ndim != 1:
+        raise exception.DataInvalid("The outcomes of state %d are not a 1-D list." % state)
+    if o.size == 0:
+        return np.zeros(0, dtype=np.int8)
+    if np.issubdtype(o.dtype, np.integer):
+        codes = o
+    else:
+        try:
+            codes = np.array([_CODE_OF[str(x)] for x in o], dtype=np.int8)
+        except KeyError as e:
+            raise exception.DataInvalid(
+                "State %d has the outcome %s; outcomes are %s or their codes 0, 1, 2."
+                % (state, e, ", ".join(OUTCOMES)))
+    if codes.min() < 0 or codes.max() > 2:
+        raise exception.DataInvalid(
+            "State %d has an outcome code outside 0, 1, 2 (%s)." % (state, ", ".join(OUTCOMES)))
+    return codes.astype(np.int8)
+
+
+def event_table(events):
+    """Compact the events of every protein state to its photon events.
+
+    events : a list over protein states of ``(lifetimes, outcomes)`` as
+        ``calc_lifetimes_many`` returns them (outcomes the reference's strings or int8
+        codes; ``([], [])`` a dyeless state), or an ``[n_states, 2]`` object array.
+
+    Returns ``EventTable(off int64 [n + 1], life float64, flag uint8, counts, n_events)``:
+    state ``s`` owns ``off[s]:off[s + 1]``, its radiative (flag 0) and energy-transfer
+    (flag 1) events in the list's own order, the non-radiative ones dropped;
+    ``counts[s]`` of them out of ``n_events[s]`` events in all.
+    """
+    if isinstance(events, EventTable):
+        return events
+    try:
+        rows = [tuple(ev) for ev in events]
+    except TypeError:
+        raise exception.DataInvalid("events is a list of (lifetimes, outcomes) per state.")
+    if not rows or any(len(ev) != 2 for ev in rows):
+        raise exception.DataInvalid("events is a non-empty list of (lifetimes, outcomes).")
+    lifes, flags, counts, totals = [], [], [], []
+    for s, (lifetimes, outcomes) in enumerate(rows):
+        try:
+            life = np.asarray(lifetimes, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise exception.DataInvalid("The lifetimes of state %d are not numbers." % s)
+        codes = _outcome_codes(outcomes, s)
+        if life.ndim != 1 or len(life) != len(codes):
+            raise exception.DataInvalid(
+                "State %d has lifetimes of shape %s for %d outcomes."
+                % (s, life.shape, len(codes)))
+        if not np.all(np.isfinite(life)):
+            raise exception.DataInvalid("The lifetimes of state %d are not finite." % s)
+        photon = codes != 1
+        if photon.sum() > _MAX_PICK:
+            raise exception.DataInvalid("State %d has 2^31 photon events or more." % s)
+        lifes.append(life[photon])
+        flags.append((codes[photon] == 2).astype(np.uint8))
+        counts.append(int(photon.sum()))
+        totals.append(len(codes))
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return EventTable(off, np.ascontiguousarray(np.concatenate(lifes), dtype=np.float64),
+                      np.ascontiguousarray(np.concatenate(flags), dtype=np.uint8),
+                      np.asarray(counts, dtype=np.int64), np.asarray(totals, dtype=np.int64))
+
+
+def _table_for(events, n_states):
+    table = event_table(events)
+    if len(table.counts) != n_states:
+        raise exception.DataInvalid(
+            "events of %d states do not fit %d protein states." % (len(table.counts), n_states))
+    return table
+
+
+def _raise_no_event(table, state):
+    if state >= 0:
+        raise exception.DataInvalid(
+            "A photon was emitted in state %d, which has %s." % (
+                state, "no event at all (a dyeless state)" if table.n_events[state] == 0
+                else "only non-radiative events, so no photon event to draw"))
+
+
+# Bounds on one device call's buffers, as in dyes_from_expt_dist (a call lasts as long as its
+# longest burst, however few bursts it holds): 4 GiB of trajectories, 2^27 photons.
+_TRAJ_CELLS = 1 << 30
+_PHOTONS = 1 << 27
+_burst_ms = np.zeros(3)
+
+
+def _chain(chain, what="chain"):
+    if isinstance(chain, bool) or not isinstance(chain, (int, np.integer)) or \
+            not 0 <= chain < 2 ** 60:
+        raise exception.DataInvalid("%s is an integer in [0, 2^60), got %r" % (what, chain))
+    return int(chain)
+
+
+def _null(t):
+    return ctypes.cast(None, ctypes.POINTER(t))
+
+
+def _run_bursts(sampler, populations, MSM_frames, random_state, return_trajectories, step_cap,
+                outputs, call, first_burst=0):
+    """The chunk loop of every explicit-dye burst sampler: cuts the bursts into device
+    calls within ``_PHOTONS`` and ``_TRAJ_CELLS``.
+
+    outputs : list of dtypes of the per-photon outputs after the flag byte
+    call(L, h, seed, b0, nb, sub_off, sub_frames, pop, cap, [flags, *outs], traj) -> None
+        one device call on bursts ``first_burst + b0 ..``; it raises what its rule flags
+
+    -> (foff, [flags uint8, *outputs] flat, trajs or None)
+    """
+    n = sampler.n_states
+    pop = dyes._pop_cdf(populations, n)
+    foff, frames = dyes._frames(MSM_frames)
+    cap = _positive(step_cap, "step_cap")
+    first = _chain(first_burst, "first burst")
+    n_bursts = len(foff) - 1
+    if first + n_bursts > 2 ** 60:
+        raise exception.DataInvalid("chains below 2^60")
+    seed = sd._seed(random_state)
+    sampler.last_seed = seed
+    global last_seed
+    last_seed = seed
+    lasts = frames[foff[1:] - 1]
+    flat = [np.empty(len(frames), dtype=np.uint8)] + \
+        [np.empty(len(frames), dtype=t) for t in outputs]
+    trajs = np.empty(n_bursts, dtype=object) if return_trajectories else None
+    h = sampler._handle()
+    L = sampler._L
+    _burst_ms[:] = 0
+    b0 = 0
+    while b0 < n_bursts:
+        # as many bursts as stay within the bounds on one call's buffers
+        cells = np.cumsum(lasts[b0:] + 1) if return_trajectories else np.zeros(1)
+        n_ph = foff[b0 + 1:] - foff[b0]
+        fit = int(np.searchsorted(n_ph, _PHOTONS, side="right"))
+        if return_trajectories:
+            fit = min(fit, int(np.searchsorted(cells, _TRAJ_CELLS, side="right")))
+        b1 = min(n_bursts, b0 + max(1, fit))
+        sub_off = np.ascontiguousarray(foff[b0:b1 + 1] - foff[b0])
+        sub_frames = frames[foff[b0]:foff[b1]]
+        subs = [a[foff[b0]:foff[b1]] for a in flat]
+        traj = np.empty(int(cells[b1 - b0 - 1]), dtype=np.int32) if return_trajectories else None
+        call(L, h, seed, first + b0, b1 - b0, sub_off, sub_frames, pop, cap, subs,
+             _lib.i32p(traj) if traj is not None else _null(ctypes.c_int32))
+        _burst_ms[:] += last_burst_timing()
+        if return_trajectories:
+            ends = cells[:b1 - b0]
+            for i in range(b1 - b0):
+                trajs[b0 + i] = traj[ends[i] - lasts[b0 + i] - 1:ends[i]]
+        b0 = b1
+    return foff, flat, trajs
+
+
+def _lifetime_call(table):
+    def call(L, h, seed, b0, nb, sub_off, sub_frames, pop, cap, subs, traj):
+        bad_row, bad_state = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        _lib.check(L.ek_dye_bursts_lifetimes(
+            h, seed, b0, nb, _lib.i64p(sub_off), _lib.i64p(sub_frames), _lib.f64p(pop),
+            _lib.i64p(table.off), _lib.f64p(table.life), _lib.u8p(table.flag), cap,
+            _lib.u8p(subs[0]), _lib.f64p(subs[1]), _lib.i32p(subs[2]), traj,
+            ctypes.byref(bad_row), ctypes.byref(bad_state)))
+        sd._raise_bad_row(bad_row.value)
+        _raise_no_event(table, bad_state.value)
+    return call
+
+
+def _ragged(flat, foff):
+    return ra.RaggedArray(flat, lengths=np.diff(foff), copy=False)
+
+
+def sample_lifetime_bursts(T, populations, events, MSM_frames, random_state=None,
+                           return_trajectories=False, device=0, step_cap=None):
+    """Bursts of photons with lifetimes: every burst runs a chain of the protein MSM and,
+    at every frame of ``MSM_frames``, draws one of the photon events of the state the
+    chain is in (the batch form of the reference's ``sample_lifetimes_guarenteed_photon``).
+
+    T : array or scipy sparse matrix, or a ``synthetic_data.Sampler``
+    populations : array, shape=(n_states,); every burst's chain starts from a draw of them
+    events : what ``calc_lifetimes_many`` returns, or an ``event_table`` of it
+    MSM_frames : list of lists, per burst the frames of its photons
+
+    Returns ``(photons uint8, lifetimes float64, states int32)``, RaggedArrays of a row
+    per burst (1: acceptor photon, 0: donor photon; the lifetime of the event drawn; the
+    state the chain was in), and with ``return_trajectories`` the chains as an object
+    array of int32 arrays.  Burst ``b`` is chain ``b`` of the seed: the chain of
+    ``dyes_from_expt_dist.sample_FRET_histograms`` and of ``simulate_burst_k2``.
+    """
+    sampler, own = sd._sampler(T, device)
+    try:
+        table = _table_for(events, sampler.n_states)
+        foff, flat, trajs = _run_bursts(
+            sampler, populations, MSM_frames, random_state, return_trajectories, step_cap,
+            [np.float64, np.int32], _lifetime_call(table))
+    finally:
+        if own:
+            sampler.close()
+    out = tuple(_ragged(a, foff) for a in flat)
+    return out + (trajs,) if return_trajectories else out
+
+
+def sample_lifetimes_guarenteed_photon(frames, t_probs, eqs, lifetimes, outcomes, rng_seed=None,
+                                       chain=0, device=0):
+    """One burst: ``(photons, lifetimes, trj[frames])`` for the frames of its photons
+    (the reference's signature; ``lifetimes``, ``outcomes``: per protein state).  It is
+    burst ``chain`` of ``sample_lifetime_bursts`` with the same seed."""
+    sampler, own = sd._sampler(t_probs, device)
+    try:
+        table = _table_for(list(zip(lifetimes, outcomes)), sampler.n_states)
+        _, flat, _ = _run_bursts(sampler, eqs, [frames], rng_seed, False, None,
+                                 [np.float64, np.int32], _lifetime_call(table),
+                                 first_burst=chain)
+    finally:
+        if own:
+            sampler.close()
+    return flat[0], flat[1], flat[2]
+
+
+def _sample_lifetimes_guarenteed_photon(states, lifetimes, outcomes, rng_seed=None, chain=0,
+                                        device=0):
+    """A photon event for every entry of ``states`` -> ``(photons uint8, lifetimes)``.
+    Entry *k* draws what photon *k* of burst ``chain`` draws."""
+    table = event_table(list(zip(lifetimes, outcomes)))
+    s = sd._states(states, len(table.counts), "states")
+    chain = _chain(chain)
+    global last_seed
+    last_seed = seed = sd._seed(rng_seed)
+    photons, life = np.empty(len(s), dtype=np.uint8), np.empty(len(s))
+    bad = ctypes.c_int64(-1)
+    _lib.check(_lib.load().ek_dye_photons_lifetimes(
+        int(device), seed, chain, len(s), _lib.i32p(s), len(table.counts), _lib.i64p(table.off),
+        _lib.f64p(table.life), _lib.u8p(table.flag), _lib.u8p(photons), _lib.f64p(life),
+        ctypes.byref(bad)))
+    _raise_no_event(table, bad.value)
+    return photons, life
+
+
+def pick_events(table, states, u, device=0):
+    """The pick of the lifetime rule with the caller's own doubles ``u`` in [0, 1): for
+    every entry the index ``min(m - 1, int(u m))`` among the ``m`` photon events of its
+    state (``table``: an ``event_table`` or events).  -> int64 array."""
+    table = event_table(table)
+    shape = np.shape(states)
+    s = sd._states(states, len(table.counts), "states")
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(-1))
+    if u.shape != s.shape:
+        raise exception.DataInvalid("%d doubles for %d states" % (len(u), len(s)))
+    if not np.all((u >= 0) & (u < 1)):
+        raise exception.DataInvalid("u must lie in [0, 1).")
+    out = np.empty(len(s), dtype=np.int64)
+    bad = ctypes.c_int64(-1)
+    _lib.check(_lib.load().ek_dye_pick_events(
+        int(device), len(s), _lib.i32p(s), _lib.f64p(u), len(table.counts),
+        _lib.i64p(table.off), _lib.i64p(out), ctypes.byref(bad)))
+    _raise_no_event(table, bad.value)
+    return out.reshape(shape)
+
+
+def extract_fret_efficiency_lifetimes(lifetime_samples):
+    """``(FEs, d_lifetimes, a_lifetimes)`` of bursts: per burst the share of acceptor
+    photons and the lifetimes behind its donor and its acceptor photons (object arrays of
+    a float array per burst).
+
+    lifetime_samples : per burst ``(photons, lifetimes, ...)`` as repeated calls of
+        ``sample_lifetimes_guarenteed_photon`` give them, or the tuple of RaggedArrays
+        ``sample_lifetime_bursts`` returns.
+    """
+    if isinstance(lifetime_samples, tuple) and len(lifetime_samples) >= 2 and \
+            all(isinstance(x, ra.RaggedArray) for x in lifetime_samples[:2]):
+        bursts = list(zip(lifetime_samples[0], lifetime_samples[1]))
+    else:
+        try:
+            bursts = [(b[0], b[1]) for b in lifetime_samples]
+        except (TypeError, IndexError):
+            raise exception.DataInvalid(
+                "lifetime_samples is a list of (photons, lifetimes) per burst.")
+    if not bursts:
+        raise exception.DataInvalid("No bursts were given.")
+    FEs = np.empty(len(bursts))
+    d_lifetimes, a_lifetimes = (np.empty(len(bursts), dtype=object) for _ in range(2))
+    for i, (photons, life) in enumerate(bursts):
+        photons, life = np.asarray(photons), np.asarray(life, dtype=np.float64)
+        if photons.ndim != 1 or photons.shape != life.shape or photons.size == 0:
+            raise exception.DataInvalid(
+                "Burst %d has photons of shape %s and lifetimes of shape %s."
+                % (i, photons.shape, life.shape))
+        FEs[i] = np.sum(photons) / len(photons)
+        d_lifetimes[i] = life[np.where(photons == 0)[0]]
+        a_lifetimes[i] = life[np.where(photons == 1)[0]]
+    return FEs, d_lifetimes, a_lifetimes
+
+
+def remake_prot_MSM_from_lifetimes(lifetimes, prot_tcounts, prot_eqs=None, device=0):
+    """The protein MSM without the states that could not be labelled (those whose entry
+    of ``lifetimes`` is empty): their rows and columns of the counts zeroed,
+    row-normalised.  -> ``(new_tprobs, new_eqs)``; the equilibrium probability of a
+    removed state is exactly 0, so no burst starts there.  Messages go to ``logging``;
+    nothing is written."""
+    prot_tcounts = np.asarray(prot_tcounts)
+    if prot_tcounts.ndim != 2 or prot_tcounts.shape[0] != prot_tcounts.shape[1]:
+        raise exception.DataInvalid("prot_tcounts is square, not %s" % (prot_tcounts.shape,))
+    n = len(prot_tcounts)
+    try:
+        n_rows = len(lifetimes)
+    except TypeError:
+        raise exception.DataInvalid("lifetimes is a list of lifetimes per protein state.")
+    if n_rows != n:
+        raise exception.DataInvalid("lifetimes of %d states do not fit %d protein states."
+                                    % (n_rows, n))
+    if prot_eqs is not None:
+        prot_eqs = np.asarray(prot_eqs, dtype=np.float64)
+        if prot_eqs.shape != (n,):
+            raise exception.DataInvalid(
+                "prot_eqs of shape %s do not fit %d states." % (prot_eqs.shape, n))
+    bad = np.asarray(r0c.find_dyeless_states(lifetimes), dtype=np.int64)
+    if len(bad) == n:
+        raise exception.DataInvalid("No protein state could be labelled.")
+    _log.info("%d of %d protein states had steric clashes.", len(bad), n)
+    if len(bad) / n > 0.2:
+        _log.warning("Labeling lost %d%% of the MSM states.", round(100 * len(bad) / n))
+    if prot_eqs is not None and len(bad):
+        lost = float(np.sum(prot_eqs[bad]))
+        _log.info("This was %.2f%% of the original equilibrium probability.", 100 * lost)
+        if lost > 0.2:
+            _log.warning("Lots of equilibrium probability lost.")
+    trimmed = r0c.remove_bad_states(bad, prot_tcounts)
+    _, new_tprobs, new_eqs = builders.normalize(trimmed, calculate_eq_probs=True, device=device)
+    new_eqs = np.array(new_eqs, dtype=np.float64)
+    new_eqs[bad] = 0.0      # (nothing enters a removed state: exactly 0, not the solver's rounding)
+    return new_tprobs, new_eqs
+
+
+def run_mc(events, prot_tcounts, MSM_frames, prot_eqs=None, random_state=None,
+           return_trajectories=False, device=0, step_cap=None):
+    """Remake the protein MSM without its dyeless states, sample a burst per entry of
+    ``MSM_frames`` and extract -> ``(FEs, d_lifetimes, a_lifetimes, photons, states)``
+    (with ``return_trajectories`` also the chains).  Nothing is written."""
+    table = event_table(events)
+    new_tprobs, new_eqs = remake_prot_MSM_from_lifetimes(
+        [np.zeros(k) for k in table.n_events], prot_tcounts, prot_eqs=prot_eqs, device=device)
+    out = sample_lifetime_bursts(new_tprobs, new_eqs, table, MSM_frames,
+                                 random_state=random_state,
+                                 return_trajectories=return_trajectories, device=device,
+                                 step_cap=step_cap)
+    FEs, d_lifetimes, a_lifetimes = extract_fret_efficiency_lifetimes(out[:3])
+    return (FEs, d_lifetimes, a_lifetimes, out[0], out[2]) + tuple(out[3:])
+
+
+def last_burst_timing():
+    """Milliseconds between device events of the last device call of the burst samplers:
+    upload, kernels, download (``burst_timing``: summed over a sampler's calls)."""
+    ms = np.zeros(3)
+    _lib.check(_lib.load().ek_dye_bursts_last_timing(_lib.f64p(ms)))
+    return ms
+
+
+def burst_timing():
+    """``last_burst_timing`` summed over the device calls of the last burst sampler"""
+    return _burst_ms.copy()

@@ -1018,6 +1018,58 @@ int ek_dye_pair_static(ek_dye_pair *h, uint64_t seed, int64_t first_chain, int64
                        int32_t *astate_out);
 int ek_dye_pair_last_timing(double *ms_out);
 
+/* ---- smFRET bursts with explicit dyes: lifetime and kappa-squared photons --------------
+ * Replaces the burst-level functions of enspara/geometry/dye_lifetimes.py
+ * (sample_lifetimes_guarenteed_photon, run_mc) and explicit_r0_calc.py (sample_dye_coords,
+ * simulate_burst_k2) (csrc/ek_dye_bursts.hip).  All arrays are host memory.
+ * The bursts, their frames, pop_cdf, step_cap, traj_out and the chain of burst b are those of
+ * ek_kmc_fret_bursts: the same seed gives the same states under either rule.  Photon k of
+ * burst b draws from (seed, chain first_burst + b, index k) on streams 9 the photon event,
+ * 10 the donor's conformation, 11 the acceptor's; the coin of the second rule is stream 4.
+ * pick(u, m) = min(m - 1, (int64)(u * (double)m)); every list has fewer than 2^31 entries.
+ * ek_dye_bursts_lifetimes: per state s the photon events ev_off[s] .. ev_off[s + 1] with
+ * lifetimes ev_life and flags ev_flag (0 donor, 1 acceptor).  Photon k takes the entry
+ * ev_off[s] + pick(u, m_s) of the state s its chain is in: flags_out[k], life_out[k];
+ * states_out[k] = s.  bad_row_out as bad_out of ek_kmc_fret_bursts; bad_state_out: -1, or the
+ * smallest state without an entry that had to serve a photon (its outputs are 0).
+ * ek_dye_bursts_k2: per state the donor's conformations d_off[s] .. d_off[s + 1] (rows of 9
+ * doubles in d_xyz: emission centre, dipole origin, dipole vector) and the acceptor's.
+ * Photon k takes donor row i = pick(u_10, nd_s), acceptor row j = pick(u_11, na_s); k2_out,
+ * r_out as ek_dye_pair_table computes them, FE = c6 k2 / (c6 k2 + r^6) with r^6 = (r r)^3 of
+ * the unrooted r^2, flags_out[k] = 1 iff the coin <= FE; drow_out, arow_out: null, or i and j
+ * (both or neither).  bad_state_out: a state one of whose dyes has no conformation.
+ * ek_dye_photons_lifetimes, ek_dye_photons_k2: the same rules on a list of states: entry k
+ * draws what photon k of burst `chain` draws.
+ * ek_dye_pick_events: index_out[k] = pick(u[k], m of states[k]) with the caller's doubles
+ * (0 <= u < 1, EK_EARG otherwise), -1 where the state has no entry.
+ * ek_dye_bursts_last_timing: ms_out[3] = upload, kernels, download of the last call. */
+int ek_dye_bursts_lifetimes(ek_kmc *h, uint64_t seed, int64_t first_burst, int64_t n_bursts,
+                            const int64_t *frame_off, const int64_t *frames,
+                            const double *pop_cdf, const int64_t *ev_off, const double *ev_life,
+                            const uint8_t *ev_flag, int64_t step_cap, uint8_t *flags_out,
+                            double *life_out, int32_t *states_out, int32_t *traj_out,
+                            int64_t *bad_row_out, int64_t *bad_state_out);
+int ek_dye_bursts_k2(ek_kmc *h, uint64_t seed, int64_t first_burst, int64_t n_bursts,
+                     const int64_t *frame_off, const int64_t *frames, const double *pop_cdf,
+                     const int64_t *d_off, const double *d_xyz, const int64_t *a_off,
+                     const double *a_xyz, double c6, int64_t step_cap, uint8_t *flags_out,
+                     double *k2_out, double *r_out, int32_t *states_out, int32_t *drow_out,
+                     int32_t *arow_out, int32_t *traj_out, int64_t *bad_row_out,
+                     int64_t *bad_state_out);
+int ek_dye_photons_lifetimes(int device, uint64_t seed, int64_t chain, int64_t n,
+                             const int32_t *states, int32_t n_states, const int64_t *ev_off,
+                             const double *ev_life, const uint8_t *ev_flag, uint8_t *flags_out,
+                             double *life_out, int64_t *bad_state_out);
+int ek_dye_photons_k2(int device, uint64_t seed, int64_t chain, int64_t n, const int32_t *states,
+                      int32_t n_states, const int64_t *d_off, const double *d_xyz,
+                      const int64_t *a_off, const double *a_xyz, double c6, uint8_t *flags_out,
+                      double *k2_out, double *r_out, int32_t *drow_out, int32_t *arow_out,
+                      int64_t *bad_state_out);
+int ek_dye_pick_events(int device, int64_t n, const int32_t *states, const double *u,
+                       int32_t n_states, const int64_t *ev_off, int64_t *index_out,
+                       int64_t *bad_state_out);
+int ek_dye_bursts_last_timing(double *ms_out);
+
 /* ---- dihedral angles and buffered rotamer states ------------------------------------
  * Replaces enspara/geometry/rotamer.py (csrc/ek_rotamer.hip).  All arrays are host
  * memory.  A dihedral is of one of n_kinds kinds (kind [n] bytes); kind k has

@@ -57,6 +57,7 @@ SYMBOLS = [
     "ek_cards_disorder_codes", "ek_cards_matrices", "ek_cards_counts",
     "ek_cards_last_timing", "ek_cards_close", "ek_cards_scan_chunk",
     "ek_sasa_open", "ek_sasa_run", "ek_sasa_last_timing", "ek_sasa_close",
+    "ek_rmsf_open", "ek_rmsf_run", "ek_rmsf_fetch", "ek_rmsf_last_timing", "ek_rmsf_close",
     "ek_wmi_run", "ek_wmi_last_timing",
     "ek_ent_kl_rows", "ek_ent_js_rows", "ek_ent_shannon_rows", "ek_ent_kl_counts",
     "ek_ent_last_timing", "ek_ent_state_counts_open", "ek_ent_state_counts_add",
@@ -282,6 +283,12 @@ def load():
     L.ek_sasa_run.argtypes = [vp, f32p, i64, i64, i32p, f32p, f32p]
     L.ek_sasa_last_timing.argtypes = [vp, f64p]
     L.ek_sasa_close.argtypes = [vp]
+    L.ek_rmsf_open.argtypes = [C.c_int, i32, i32, i32p, f32p, i32, i32p, i32p, C.POINTER(vp)]
+    L.ek_rmsf_run.argtypes = [vp, f32p, i64, f64p, i64, i64, f32p, f64p, f32p,
+                              C.POINTER(C.c_uint32)]
+    L.ek_rmsf_fetch.argtypes = [vp, f64p, f64p]
+    L.ek_rmsf_last_timing.argtypes = [vp, f64p]
+    L.ek_rmsf_close.argtypes = [vp]
     L.ek_wmi_run.argtypes = [C.c_int, u8p, f64p, i64, i32, i32, f64p, f64p]
     L.ek_wmi_last_timing.argtypes = [f64p]
     L.ek_ent_kl_rows.argtypes = [C.c_int, i64, i64, f64p, f64p, f64p, u32p]

@@ -135,6 +135,42 @@ __device__ __forceinline__ float ek_rmsd_from_S(const float (&S)[9], double Gx,
     return __builtin_sqrtf((float)ek_msd_from_S(S, Gx, Gy, n_atoms));
 }
 
+// ek_msd_from_S, operation for operation, that also hands out the root the
+// iteration ended at: the superposition (ek_superpose.h) builds its rotation
+// from K - lam I.  A copy, so that the function above keeps its code.
+__device__ __forceinline__ double ek_msd_lambda_from_S(const float (&S)[9], double Gx,
+                                                       double Gy, int n_atoms,
+                                                       double *lam_out)
+{
+    const EkQuartic p = ek_quartic_from_S(S);
+    const double q = p.q, C2 = p.C2, C1 = p.C1, C0 = p.C0;
+    const double Gsum = Gx + Gy;
+    const double top = 0.5 * Gsum;
+    double lam = top;
+    for (int it = 0; it < EK_MAXIT; ++it) {
+        const double x2 = lam * lam;
+        const double b = (x2 + C2) * lam;
+        const double a = b + C1;
+        const double num = __builtin_fma(a, lam, C0);
+        const double den = __builtin_fma(2.0 * x2, lam, b + a);
+        if (den == 0.0)
+            break;
+        const double delta = num / den;
+        const double nxt = lam - delta;
+        // (the step rule of ek_msd_from_S)
+        if (!(nxt > 0.0 && nxt <= top && 3.0 * (nxt * nxt) >= q))
+            break;
+        lam = nxt;
+        if (__builtin_fabs(delta) < __builtin_fabs(EK_EVALPREC * lam))
+            break;
+    }
+    *lam_out = lam;
+    double msd = (Gsum - 2.0 * lam) / (double)n_atoms;
+    if (!(msd > 0.0))
+        msd = 0.0;
+    return msd;
+}
+
 // ---- a float32 certificate for FAR pairs, before any float64 coefficient --------------
 //
 // Most distances a pass computes are never used: the pair is far, all a strict

@@ -733,6 +733,42 @@ int ek_sasa_run(ek_sasa *h, const float *xyz, int64_t frames, int64_t chunk_fram
 int ek_sasa_last_timing(ek_sasa *h, double *ms_out);
 int ek_sasa_close(ek_sasa *h);
 
+/* ---- Superposition and weighted RMSF ---------------------------------------------------
+ * Replaces enspara/geometry/rmsf.py and the md.Trajectory.superpose it calls
+ * (csrc/ek_rmsf.hip, csrc/ek_superpose.h; the contract is DESIGN.md 4o).  A handle holds,
+ * on the device, the n_sel >= 3 atoms `sel` (each in [0, atoms)) that define the fit, the
+ * reference structure [atoms][3] (finite), its selection centred, and the running sums;
+ * on the host n_groups >= 0 groups of atoms, group g = group_atoms[group_offsets[g] ..
+ * group_offsets[g + 1]), none empty (EK_EARG otherwise).  All arrays are host memory.
+ * ek_rmsf_run: xyz [frames][atoms][3] float32, finite (the caller's to check).  Every frame
+ * is superposed on the reference over the selection: centroid in float64, centred
+ * coordinates and the 3x3 inner products rounded to float32, the largest root by the
+ * iteration of the RMSD kernels, the rotation from the adjugate of K - lambda I in float64;
+ * aligned_out [frames][atoms][3] = float32(R (x - centroid) + the reference selection's
+ * centroid), rotations_out [frames][9] row-major, rmsd_out [frames] over the selection;
+ * each may be null.  flags_out [frames] (required): bit 0 = the rotation is not determined
+ * (gap of the two largest eigenvalues <= 2e-5 (Gx + Gy)); such a frame gets the identity.
+ * Frame ref_index (-1: none) is taken as it is: the identity, its own bits.  weights
+ * [frames] float64 (null: no sums): sums_a += w_f |aligned_fa - reference_a|^2 in float64,
+ * per tile of 32 frames (absolute indices over all runs of the handle) in frame order, the
+ * tiles then in order: the bits do not depend on chunk_frames or on how the frames are cut
+ * into runs.  chunk_frames > 0: frames of one upload and launch; 0: what fits half of the
+ * free device memory.
+ * ek_rmsf_fetch: atom_sums_out [atoms] and group_sums_out [n_groups] = the sum of a group's
+ * atom sums in listed order, divided by their count; each may be null.
+ * ek_rmsf_last_timing: ms_out[3] = the last run's uploads, kernels and downloads, summed
+ * over its chunks, between HIP events. */
+typedef struct ek_rmsf ek_rmsf;
+int ek_rmsf_open(int device, int32_t atoms, int32_t n_sel, const int32_t *sel,
+                 const float *reference, int32_t n_groups, const int32_t *group_offsets,
+                 const int32_t *group_atoms, ek_rmsf **out);
+int ek_rmsf_run(ek_rmsf *h, const float *xyz, int64_t frames, const double *weights,
+                int64_t ref_index, int64_t chunk_frames, float *aligned_out,
+                double *rotations_out, float *rmsd_out, uint32_t *flags_out);
+int ek_rmsf_fetch(ek_rmsf *h, double *atom_sums_out, double *group_sums_out);
+int ek_rmsf_last_timing(ek_rmsf *h, double *ms_out);
+int ek_rmsf_close(ek_rmsf *h);
+
 /* ---- LIGSITE pocket detection ---------------------------------------------------------
  * Replaces enspara/geometry/pockets.py (csrc/ek_pockets.hip; the contract is DESIGN.md
  * 4i).  A handle holds, on the device, cutoff [atoms] float64 = probe + radius in nm (> 0

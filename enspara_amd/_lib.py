@@ -49,6 +49,8 @@ SYMBOLS = [
     "ek_pam_propose_center",
     "ek_msm_counts", "ek_msm_counts_ctx", "ek_msm_row_normalize",
     "ek_msm_mle_prinz", "ek_msm_bace_prune", "ek_msm_bace_run",
+    "ek_msm_boot_open", "ek_msm_boot_fetch", "ek_msm_boot_build", "ek_msm_boot_last_timing",
+    "ek_msm_boot_close",
     "ek_lu_solve", "ek_lu_set_timing", "ek_lu_last_timing",
     "ek_tpt_committors", "ek_tpt_mfpts_sinks", "ek_tpt_mfpts_all", "ek_tpt_fluxes",
     "ek_mi_open", "ek_mi_add", "ek_mi_load_counts", "ek_mi_counts", "ek_mi_information",
@@ -252,6 +254,12 @@ def load():
     L.ek_msm_bace_prune.argtypes = [C.c_int, i32, f64p, f64p, f32p]
     L.ek_msm_bace_run.argtypes = [C.c_int, i32, f64p, f64p, i32p, i32, i32, i32, vp,
                                   i32, f32p]
+    L.ek_msm_boot_open.argtypes = [C.c_int, i32p, i64p, i64, i32, i32, i32, i64, i64p, i32p,
+                                   i32, i32p, i32, C.POINTER(vp)]
+    L.ek_msm_boot_fetch.argtypes = [vp, i32, i32, i64p]
+    L.ek_msm_boot_build.argtypes = [vp, i64, i64p, i64p, i64p, f64p, f64p]
+    L.ek_msm_boot_last_timing.argtypes = [vp, f64p]
+    L.ek_msm_boot_close.argtypes = [vp]
     L.ek_lu_solve.argtypes = [C.c_int, i32, f64p, i32, f64p, f64p, i32p, i32p]
     L.ek_lu_set_timing.argtypes = [C.c_int]
     L.ek_lu_last_timing.argtypes = [f64p, f64p]

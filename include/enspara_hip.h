@@ -769,6 +769,41 @@ int ek_rmsf_fetch(ek_rmsf *h, double *atom_sums_out, double *group_sums_out);
 int ek_rmsf_last_timing(ek_rmsf *h, double *ms_out);
 int ek_rmsf_close(ek_rmsf *h);
 
+/* ---- Bootstrapped transition counts -----------------------------------------------------
+ * Replaces the per-trial loop of enspara/msm/bootstrap.py (csrc/ek_msm_boot.hip; the
+ * contract is DESIGN.md 4p).  A trial draws units (trajectories or blocks of them) with
+ * replacement; its counts are sum_u mult[u][trial] * (counts of unit u) and live on the
+ * sparsity pattern of the full data's counts.  All arrays are host memory.
+ * ek_msm_boot_open: assigns = the units' frames one after the other (-1 = no state, dropped
+ * per unit before pairing, as ek_msm_counts does), lengths [n_units] >= 0; the pattern as
+ * CSR over n_states rows: indptr [n_states + 1], cols [nnz] ascending inside a row; mult
+ * [n_units][R] int32, R = n_trials rounded up to a multiple of 64, the padding zero.  One
+ * pass over the frames fills the table [nnz][R] int32, which stays on the device: the
+ * caller guarantees that no cell of a trial reaches 2^31.  chunk = consecutive positions
+ * one wave of the scatter walks (0: 256); the table's bytes do not depend on it.  A state
+ * outside [0, n_states) is EK_EARG; a transition of the frames that the pattern does not
+ * hold is EK_ESTATE.
+ * ek_msm_boot_fetch: out [r1 - r0][nnz] int64 = the counts of trials r0 .. r1 - 1.
+ * ek_msm_boot_build: row normalisation of every trial on the symmetrised pattern S (nnzS
+ * cells, CSR indptrS over n_states rows): cell j of S is table cell idx_ij[j] plus table
+ * cell idx_ji[j], each -1 for none; v = their integer sum, w = the row's exact sum,
+ * probs_out [n_trials][nnzS] = ((w > 0) ? 1 / w : 0) * v, rowsum_out [n_trials][n_states]
+ * = w: the two roundings of ek_msm_row_normalize.
+ * ek_msm_boot_last_timing: ms_out[3] = squeeze and cells, the scatter, the last build,
+ * between HIP events. */
+typedef struct ek_msm_boot ek_msm_boot;
+int ek_msm_boot_open(int device, const int32_t *assigns, const int64_t *lengths,
+                     int64_t n_units, int32_t lag_time, int32_t sliding_window,
+                     int32_t n_states, int64_t nnz, const int64_t *indptr,
+                     const int32_t *cols, int32_t n_trials, const int32_t *mult,
+                     int32_t chunk, ek_msm_boot **out);
+int ek_msm_boot_fetch(ek_msm_boot *h, int32_t r0, int32_t r1, int64_t *out);
+int ek_msm_boot_build(ek_msm_boot *h, int64_t nnzS, const int64_t *indptrS,
+                      const int64_t *idx_ij, const int64_t *idx_ji, double *probs_out,
+                      double *rowsum_out);
+int ek_msm_boot_last_timing(ek_msm_boot *h, double *ms_out);
+int ek_msm_boot_close(ek_msm_boot *h);
+
 /* ---- LIGSITE pocket detection ---------------------------------------------------------
  * Replaces enspara/geometry/pockets.py (csrc/ek_pockets.hip; the contract is DESIGN.md
  * 4i).  A handle holds, on the device, cutoff [atoms] float64 = probe + radius in nm (> 0

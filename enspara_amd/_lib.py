@@ -76,6 +76,8 @@ SYMBOLS = [
     "ek_pockets_labels",
     "ek_dyes_open", "ek_dyes_run", "ek_dyes_counts", "ek_dyes_fetch", "ek_dyes_last_timing",
     "ek_dyes_close", "ek_dyes_touches", "ek_dyes_pair_hist",
+    "ek_dye_map_open", "ek_dye_map_max_centres", "ek_dye_map_run", "ek_dye_map_fetch",
+    "ek_dye_map_stats", "ek_dye_map_last_timing", "ek_dye_map_close",
     "ek_rotamer_states", "ek_dihedral_angles", "ek_dihedral_rotamers",
     "ek_krylov_create", "ek_krylov_destroy", "ek_krylov_set_vector",
     "ek_krylov_get_vector", "ek_krylov_step", "ek_krylov_rotate",
@@ -360,6 +362,14 @@ def load():
     L.ek_dyes_close.argtypes = [vp]
     L.ek_dyes_touches.argtypes = [C.c_int, f32p, i32, f64p, f32p, i32, u8p]
     L.ek_dyes_pair_hist.argtypes = [C.c_int, f32p, i32, f32p, i32, C.c_double, i32p, i64p]
+    L.ek_dye_map_open.argtypes = [C.c_int, i32, f64p, i32, i32p, i32, i32, f32p, i32, i32p, i32p,
+                                  i32, i32, i32, C.POINTER(vp)]
+    L.ek_dye_map_max_centres.argtypes = [vp, i32, C.POINTER(i64)]
+    L.ek_dye_map_run.argtypes = [vp, f32p, i64, i32]
+    L.ek_dye_map_fetch.argtypes = [vp, i64, i32p, f64p, u8p, f32p]
+    L.ek_dye_map_stats.argtypes = [vp, i64, i32p, f64p]
+    L.ek_dye_map_last_timing.argtypes = [vp, f64p]
+    L.ek_dye_map_close.argtypes = [vp]
     L.ek_rotamer_states.argtypes = [C.c_int, f32p, i64, i32, u8p, i32, i32p, f64p, f32p,
                                     C.c_double, u8p, f64p]
     L.ek_dihedral_angles.argtypes = [C.c_int, f32p, i64, i32, i32p, i32, f32p, f64p]

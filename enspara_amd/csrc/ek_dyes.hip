@@ -44,6 +44,7 @@
 // diagonal of the box that holds a frame's four placements must be below 4093 bin widths
 // (EK_EARG), and coordinates at most 2^20 nm.
 #include "ek_common.h"
+#include "ek_sq_threshold.h"
 
 #include <math.h>
 #include <new>
@@ -75,18 +76,7 @@ int ek_mi_check_memory(size_t bytes, const char *who);
 #define DY_MAX_WIDTH 0x1p40
 
 // ---- host: the thresholds ------------------------------------------------------------------
-// the smallest double s >= 0 with sqrt(s) >= e
-static double dy_sq_at_least(double e)
-{
-    if (!(e > 0.0))
-        return 0.0;
-    double s = e * e;
-    while (s > 0.0 && sqrt(nextafter(s, 0.0)) >= e)
-        s = nextafter(s, 0.0);
-    while (sqrt(s) < e)
-        s = nextafter(s, INFINITY);
-    return s;
-}
+// (dy_sq_at_least, the smallest double s >= 0 with sqrt(s) >= e: ek_sq_threshold.h)
 
 // the smallest double x >= 0 with x / w >= m
 static double dy_div_at_least(double m, double w)

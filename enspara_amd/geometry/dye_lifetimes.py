@@ -74,11 +74,13 @@ is its first step).  On purpose different from the reference here:
   messages go to ``logging``, no file is read or written, and a removed state's
   equilibrium probability is exactly 0, as in ``make_dye_msm``.
 
-Not ported: ``load_dye``, ``load_library``, ``get_dye_overlap`` (files, yaml, pandas);
-``align_full_dye_to_res``, ``remove_touches_protein_dye_traj`` (mdtraj: the caller
-passes aligned coordinates and ``keep``; the touch test itself is
-``dyes_from_expt_dist.remove_touches_protein``); the ``curve_fit`` helpers (scipy on
-the host); the ``save_*`` file outputs.
+Labelling: ``explicit_r0_calc.map_dye_on_protein`` places a dye library on
+a residue of every centre and finds the conformations to keep; ``centres_from_maps`` turns
+a donor's and an acceptor's map into the list ``calc_lifetimes_many`` takes, so that
+labelling -> lifetimes -> bursts is three calls.
+
+Not ported: ``load_dye``, ``load_library``, ``get_dye_overlap`` (files, yaml, pandas); the
+``curve_fit`` helpers (scipy on the host); the ``save_*`` file outputs.
 """
 import collections
 import ctypes
@@ -96,6 +98,7 @@ __all__ = ["FRET_rate", "calc_dye_radiative_rates", "calc_energy_transfer_prob",
            "calc_per_state_FE", "make_dye_msm", "OUTCOMES", "outcome_names", "problem",
            "geometry_problem", "DyePair", "resolve_excitations", "explicit_static_dyes",
            "fully_averaged_explicit_dyes", "calc_lifetimes", "calc_lifetimes_many",
+           "centres_from_maps",
            "last_seed", "last_timing", "CHUNK_BYTES", "MAX_STEPS", "EventTable", "event_table",
            "sample_lifetime_bursts", "sample_lifetimes_guarenteed_photon",
            "_sample_lifetimes_guarenteed_photon", "pick_events",
@@ -639,6 +642,28 @@ def calc_lifetimes_many(centres, dye_params, dye_lagtime, n_samples=1000,
                                  outcome_names(codes[q - k]))
         k = m + 1
     return results
+
+
+def centres_from_maps(d_map, d_tcounts, a_map, a_tcounts):
+    """The ``centres`` of ``calc_lifetimes_many`` from a donor's and an acceptor's
+    ``explicit_r0_calc.DyeMap`` of the same protein centres and the transition counts of
+    the two dye MSMs (one state per conformation of the dye library): per centre
+    ``(d_coords_all, d_tcounts, d_kept, a_coords_all, a_tcounts, a_kept)``."""
+    for m, what in ((d_map, "d_map"), (a_map, "a_map")):
+        if not all(hasattr(m, f) for f in ("coords_all", "kept")):
+            raise exception.DataInvalid("%s is what map_dye_on_protein returns." % what)
+    if len(d_map.kept) != len(a_map.kept):
+        raise exception.DataInvalid(
+            "The donor's map has %d centres, the acceptor's %d."
+            % (len(d_map.kept), len(a_map.kept)))
+    for m, t, what in ((d_map, d_tcounts, "donor"), (a_map, a_tcounts, "acceptor")):
+        shape = np.shape(t) if not hasattr(t, "shape") else t.shape
+        n = m.coords_all.shape[1]
+        if tuple(shape) != (n, n):
+            raise exception.DataInvalid(
+                "The %s's t_counts are %s; its library has %d conformations." % (what, shape, n))
+    return [(d_map.coords_all[p], d_tcounts, d_map.kept[p],
+             a_map.coords_all[p], a_tcounts, a_map.kept[p]) for p in range(len(d_map.kept))]
 
 
 def calc_lifetimes(d_coords, d_tcounts, d_keep, a_coords, a_tcounts, a_keep, dye_params,

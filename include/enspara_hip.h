@@ -912,6 +912,59 @@ int ek_dyes_touches(int device, const float *xyz, int32_t atoms, const double *c
 int ek_dyes_pair_hist(int device, const float *coords1, int32_t n1, const float *coords2,
                       int32_t n2, double bin_width, int32_t *nbins_out, int64_t *counts_out);
 
+/* ---- explicit dyes placed on a residue ---------------------------------------------------
+ * Replaces map_dye_on_protein of enspara/geometry/explicit_r0_calc.py and what it calls
+ * (align_full_dye_to_res, remove_touches_protein_dye_traj, assemble_dye_r_mu;
+ * csrc/ek_dye_map.hip; the contract is DESIGN.md 4q).  All arrays are host memory.
+ * A handle holds, on the device, cutoff [atoms] float64 = radius + probe in nm (in (0, 2^20]),
+ * the n_excl atoms `excl` the touch test skips, the dye library dye_xyz [D][A][3] float32 in
+ * nm (finite, at most 2^20 in magnitude, D * A < 2^31 - 256), the selections prot_sel and
+ * dye_sel of 3 <= n_sel <= 16 atoms each (in [0, atoms) and [0, A)), and the atoms r_atom,
+ * mu0, mu1 in [0, A) of the emission centre and the dipole.  prot_sel null: the dye
+ * coordinates are taken as they are (no fit; dye_sel and n_sel are ignored).
+ * ek_dye_map_run: xyz [centres][atoms][3] float32 in nm, finite and at most 2^20 in
+ * magnitude (the caller's to check, as for ek_rmsf_run), 1 <= centres <= 32768 (what
+ * ek_dye_map_max_centres answers fits half of the free device memory).  Per (centre p,
+ * conformation d):
+ *   fit    as ek_rmsf_run with the sums taken sequentially in selection order: the
+ *          centroids of the two selections as float64 sums, the centred coordinates
+ *          rounded to float32, S, Gx, Gy as float64 sums of the exact products, S rounded to
+ *          float32, lambda by the iteration of the RMSD kernels, R from the adjugate of K -
+ *          lambda I; flag 1 (and the identity) where the rotation is not determined (gap of
+ *          the two largest eigenvalues <= 2e-5 (Gx + Gy));
+ *   apply  aligned = float32(fma(R_i2, z, fma(R_i1, y, R_i0 * x)) + c_ref_i), (x, y, z) =
+ *          double(coordinate) - centroid of the conformation's selection;
+ *   touch  float64: a dye atom is free iff for every atom a that is not excluded (dx*dx +
+ *          dy*dy) + dz*dz >= thr_a, d = double(atom) - double(aligned), thr_a the smallest
+ *          double whose correctly rounded square root exceeds cutoff_a (made on the host):
+ *          free iff every distance > cutoff.  counts [p][d] = the free atoms, exactly.
+ *          Atoms farther from c_ref than reach + cutoff_a + margin_p are dropped before the
+ *          test, which changes no count (reach = the largest distance of a dye atom from
+ *          its conformation's selection centroid; margin_p = 2^-22 (max|c_ref| + reach) +
+ *          2^-40 reach; without a fit the centre is the mean of all dye atoms and the
+ *          margin 0);
+ *   r, mu  coords [p][d][9] = double of the aligned float32 coordinates of r_atom, of mu0,
+ *          and of their float32 difference mu0 - mu1.
+ * Counts are taken with integer atomics only: every run gives the same bits, whatever the
+ * number of centres of a run.  want_aligned != 0 keeps aligned [p][d][A][3] for the fetch.
+ * ek_dye_map_fetch: the last run's counts_out [centres][D] int32, coords_out [centres][D][9],
+ * flags_out [centres][D] bytes, aligned_out [centres][D][A][3] or null (centres must be that
+ * run's: EK_ESTATE).  ek_dye_map_stats: list_len_out [centres] = the atoms that passed the
+ * cull, *reach_out (may be null) = reach.  ek_dye_map_last_timing: ms_out[5] = the last run's
+ * upload, fit, cull and touch kernels and the last fetch's download, between HIP events. */
+typedef struct ek_dye_map ek_dye_map;
+int ek_dye_map_open(int device, int32_t atoms, const double *cutoff, int32_t n_excl,
+                    const int32_t *excl, int32_t D, int32_t A, const float *dye_xyz,
+                    int32_t n_sel, const int32_t *prot_sel, const int32_t *dye_sel,
+                    int32_t r_atom, int32_t mu0, int32_t mu1, ek_dye_map **out);
+int ek_dye_map_max_centres(ek_dye_map *h, int32_t want_aligned, int64_t *out);
+int ek_dye_map_run(ek_dye_map *h, const float *xyz, int64_t centres, int32_t want_aligned);
+int ek_dye_map_fetch(ek_dye_map *h, int64_t centres, int32_t *counts_out, double *coords_out,
+                     uint8_t *flags_out, float *aligned_out);
+int ek_dye_map_stats(ek_dye_map *h, int64_t centres, int32_t *list_len_out, double *reach_out);
+int ek_dye_map_last_timing(ek_dye_map *h, double *ms_out);
+int ek_dye_map_close(ek_dye_map *h);
+
 /* ---- joint probabilities and mutual information of weighted frames --------------------
  * Replaces the arithmetic of weighted_mi (enspara/info_theory/mutual_info.py:78-178;
  * csrc/ek_wmi.hip).  codes [frames][F] state codes as bytes (the caller validates them:

@@ -10,15 +10,20 @@ Data: uniform random blobs at protein density (170 atoms in a 1.3 nm cube), radi
 H / C / N / O, a different blob per frame; at probe 0.14 and 96 points about a third of
 the atoms are buried and the rest keep up to half of their points, so both branches of
 the point loop are at work.  Atom counts sit either side of a wave and of a 256-lane
-workgroup, point counts either side of one point per lane (100: ragged), and 2100 atoms
-take two batches of the neighbour scan."""
+workgroup.  Point counts: 1, 24, 96, 100 and 960 on 170 atoms (fewer points than lanes, and
+3.75 a lane), and on 65 atoms 255, 256 and 257 -- either side of one point per lane -- and
+MAX_POINTS - 1 and MAX_POINTS, where a lane's sixteenth point takes the last bit of its
+mask; one point more is refused.  2047, 2048 and 2049 atoms sit either side of one batch of
+the neighbour scan (exactly full; a second batch of one atom), 2100 take two batches."""
 import functools
 import os
 
 import numpy as np
 import pytest
 
+import _limit_cases as lc
 import _numpy_sasa as ns
+from enspara_amd.exception import DataInvalid
 from enspara_amd.geometry import sasa
 
 pytestmark = pytest.mark.gpu
@@ -73,10 +78,27 @@ def test_atom_counts(atoms):
         assert 0.1 < buried < 0.7 and c.max() > 20
 
 
-@pytest.mark.parametrize("n", [1, 24, 96, 100, 960])
+LANES = lc.define("ek_sasa.hip", "SASA_WG")
+SCAN = lc.define("ek_sasa.hip", "SASA_SCAN")
+
+
+@pytest.mark.parametrize("n", [1, 24, 96, 100, 960, LANES - 1, LANES, LANES + 1,
+                               sasa.MAX_POINTS - 1, sasa.MAX_POINTS])
 def test_sphere_point_counts(n):
-    xyz, radii = _blob(1, 170)
-    _check(xyz, radii, 0.14, n, _expected(1, 170, 0.14, n))
+    atoms = 170 if n in (1, 24, 96, 100, 960) else 65
+    xyz, radii = _blob(1, atoms)
+    c = _check(xyz, radii, 0.14, n, _expected(1, atoms, 0.14, n))
+    if atoms == 65:
+        # buried atoms and atoms that keep over a quarter of their points: both branches
+        assert c.min() == 0 and c.max() > n // 4
+    if n == sasa.MAX_POINTS:
+        assert n == 16 * LANES == lc.define("ek_sasa.hip", "SASA_MAX_POINTS")
+
+
+def test_one_sphere_point_too_many_is_refused():
+    xyz, radii = _blob(1, 65)
+    with pytest.raises(DataInvalid):
+        sasa.shrake_rupley(xyz, radii, n_sphere_points=sasa.MAX_POINTS + 1)
 
 
 @pytest.mark.parametrize("frames", [1, 3, 17])
@@ -97,6 +119,20 @@ def test_host_chunks(chunk):
 def test_two_batches_of_the_neighbour_scan():
     xyz, radii = _blob(1, 2100)
     c = _check(xyz, radii, 0.14, 24, _expected(1, 2100, 0.14, 24))
+    assert c.min() == 0 and c.max() > 0
+
+
+@pytest.mark.parametrize("atoms", [SCAN - 1, SCAN, SCAN + 1])
+def test_atoms_around_one_batch_of_the_neighbour_scan(atoms):
+    """SCAN atoms fill the batch exactly; with SCAN + 1 the second batch holds one atom"""
+    xyz, radii = _blob(1, atoms)
+    want = _expected(1, atoms, 0.14, 8)
+    if atoms == SCAN + 1:
+        # the lone atom of the second batch is blocked by atoms of the first, and blocks some
+        assert want[0, SCAN] < 8
+        alone = ns.counts(xyz[:, :SCAN], radii[:SCAN], 0.14, 8)
+        assert not np.array_equal(alone, want[:, :SCAN])
+    c = _check(xyz, radii, 0.14, 8, want)
     assert c.min() == 0 and c.max() > 0
 
 

@@ -10,7 +10,6 @@
 // ---- the active view's buffers (kernels: ek_view.hip; when to build one: EkViewPolicy) -------
 void ek_view_free(ek_ctx *c)
 {
-    (void)ek_dev_free(c->v_aos);
     (void)ek_dev_free(c->v_tiles);
     (void)ek_dev_free(c->v_qtiles);
     (void)ek_dev_free(c->v_G);
@@ -20,11 +19,12 @@ void ek_view_free(ek_ctx *c)
     (void)ek_dev_free(c->v_blockcnt);
     (void)ek_dev_free(c->v_blockoff);
     (void)ek_dev_free(c->v_count);
-    c->v_aos = c->v_tiles = c->v_qtiles = nullptr;
+    (void)ek_dev_free(c->v_selcnt);
+    c->v_tiles = c->v_qtiles = nullptr;
     c->v_G = nullptr;
     c->v_dist = nullptr;
     c->v_assign = nullptr;
-    c->v_act = c->v_blockcnt = c->v_blockoff = c->v_count = nullptr;
+    c->v_act = c->v_blockcnt = c->v_blockoff = c->v_count = c->v_selcnt = nullptr;
     c->view_cap = 0;
 }
 
@@ -43,7 +43,6 @@ static int ek_view_alloc(ek_ctx *c, int64_t frames)
 #define EK_VALLOC(ptr, bytes)                                                  \
     if (e == hipSuccess)                                                       \
         e = ek_malloc_named(c, (void **)&(ptr), (bytes), #ptr);
-    EK_VALLOC(c->v_aos, (size_t)cap * A3 * sizeof(float));
     EK_VALLOC(c->v_tiles, nt * A3 * EK_TILE * sizeof(float));
     EK_VALLOC(c->v_qtiles, ek_quad_tiles_bytes((int64_t)nt, c->A));
     EK_VALLOC(c->v_G, (size_t)cap * sizeof(double));
@@ -52,9 +51,12 @@ static int ek_view_alloc(ek_ctx *c, int64_t frames)
     EK_VALLOC(c->v_act, (size_t)cap * sizeof(uint32_t));
     EK_VALLOC(c->v_blockcnt, nblk * sizeof(uint32_t));
     EK_VALLOC(c->v_blockoff, nblk * sizeof(uint32_t));
-    EK_VALLOC(c->v_count, 2 * sizeof(uint32_t));
+    // (the looks' words are zeroed by the looks themselves, ek_view_look_kernel: a
+    // selection, which may come between two looks, counts into a word of its own)
+    EK_VALLOC(c->v_count, 4 * sizeof(uint32_t));
+    EK_VALLOC(c->v_selcnt, sizeof(uint32_t));
     if (e == hipSuccess)
-        e = hipMemsetAsync(c->v_count, 0, 2 * sizeof(uint32_t), c->stream);
+        e = hipMemsetAsync(c->v_count, 0, 4 * sizeof(uint32_t), c->stream);
 #undef EK_VALLOC
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -66,6 +68,7 @@ static int ek_view_alloc(ek_ctx *c, int64_t frames)
         EK_HIP(e);
     }
     c->view_cap = cap;
+    c->v_parity = 0;
     return EK_OK;
 }
 
@@ -82,9 +85,8 @@ struct EkViewRun {
 static hipError_t ek_view_poison(ek_ctx *c)
 {
     const size_t cap = (size_t)c->view_cap, nt = cap / EK_TILE, A3 = (size_t)3 * c->A;
-    hipError_t e = hipMemsetAsync(c->v_aos, 0xFF, cap * A3 * sizeof(float), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->v_tiles, 0xFF, nt * A3 * EK_TILE * sizeof(float), c->stream);
+    hipError_t e =
+        hipMemsetAsync(c->v_tiles, 0xFF, nt * A3 * EK_TILE * sizeof(float), c->stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(c->v_qtiles, 0xFF, ek_quad_tiles_bytes((int64_t)nt, c->A),
                            c->stream);
@@ -97,14 +99,15 @@ static hipError_t ek_view_poison(ek_ctx *c)
     return e;
 }
 
-// the view's store from the selection c->v_act[0 .. n_v): frame-major copy, traces,
-// distances, labels and the quad copy; without a quad copy in the context (rounds of 8
-// at most) the frame-minor tiles instead.  -> whether v_tiles holds the view
+// the view's store from the selection c->v_act[0 .. n_v): traces, distances, labels and
+// the quad copy; without a quad copy in the context (rounds of 8 at most) the frame-minor
+// tiles instead.  No frame-major copy: the rounds read the shard's through v_act
+// (ek_run_use_store).  -> whether v_tiles holds the view
 static bool ek_view_build(ek_ctx *c, int64_t n_v)
 {
     ek_launch_view_build(c->v_act, n_v, c->A, c->qt_valid, c->aos, c->G, c->dist, c->assign,
-                         c->v_aos, c->qt_valid ? c->v_qtiles : c->v_tiles, c->v_G, c->v_dist,
-                         c->v_assign, c->stream);
+                         c->qt_valid ? c->v_qtiles : c->v_tiles, c->v_G, c->v_dist, c->v_assign,
+                         c->stream);
     return !c->qt_valid;
 }
 
@@ -130,6 +133,7 @@ void ek_round_of(ek_ctx *c, int T, double cutoff, EkRound &R)
     R.tiles = c->tiles;
     R.qtiles = c->qtiles;
     R.aos = c->aos;
+    R.act = nullptr;
     R.G = c->G;
     R.recs = c->recsT;
     R.plan = c->plan;
@@ -257,7 +261,8 @@ static void ek_run_use_store(EkRun &run, bool the_view)
         R.assign = c->v_assign;
         R.tiles = c->v_tiles;
         R.qtiles = c->v_qtiles;
-        R.aos = c->v_aos;
+        R.aos = c->aos;         // (frame-major rows stay the shard's: ek_round_row)
+        R.act = c->v_act;
         R.G = c->v_G;
         R.n = run.view.n;
         R.n_pad = (run.view.n + EK_TILE - 1) / EK_TILE * EK_TILE;
@@ -267,6 +272,7 @@ static void ek_run_use_store(EkRun &run, bool the_view)
         R.tiles = c->tiles;
         R.qtiles = c->qtiles;
         R.aos = c->aos;
+        R.act = nullptr;
         R.G = c->G;
         R.n = c->n;
         R.n_pad = c->n_pad;
@@ -309,9 +315,9 @@ static int ek_run_enter_view(EkRun &run, int32_t left)
     }
     uint32_t nv = 0;
     ek_launch_view_select(c->dist, c->n, p.theta, c->v_blockcnt, c->v_blockoff, c->v_act,
-                          c->view_cap, c->v_count, c->stream);
+                          c->view_cap, c->v_selcnt, c->stream);
     EK_CHECK_LAUNCH();
-    EK_HIP(hipMemcpyAsync(&nv, c->v_count, sizeof(nv), hipMemcpyDeviceToHost, c->stream));
+    EK_HIP(hipMemcpyAsync(&nv, c->v_selcnt, sizeof(nv), hipMemcpyDeviceToHost, c->stream));
     EK_HIP(ek_wait(c));
     if (nv > 0 && (int64_t)nv < c->n && (int64_t)nv <= c->view_cap) {
         view.n = nv;
@@ -497,14 +503,14 @@ static int ek_run_carry_look(EkRun &run)
         run.view_mode = 0;      // (no memory for it: the run is what it was without)
         return EK_OK;
     }
-    EK_HIP(hipMemsetAsync(c->v_count, 0, sizeof(run.look_cnt), c->stream));
-    ek_launch_view_look(run.R.dist, run.R.n, c->ctl, run.rho, EK_VIEW_REL, EK_VIEW_ABS,
-                        c->v_count, c->stream);
-    if (run.view.on)
-        ek_launch_view_look(c->dist, c->n, c->ctl, run.rho, EK_VIEW_REL, EK_VIEW_ABS,
-                            c->v_count + 1, c->stream);
+    // one launch: the store being streamed and, under a view, the shard's distances;
+    // the counts into this look's pair of words, the last look's pair zeroed for the next
+    const int parity = c->v_parity;
+    ek_launch_view_look(run.R.dist, run.R.n, run.view.on ? c->dist : nullptr, c->n, c->ctl,
+                        run.rho, EK_VIEW_REL, EK_VIEW_ABS, c->v_count, parity, c->stream);
     EK_CHECK_LAUNCH();
-    EK_HIP(hipMemcpyAsync(run.look_cnt, c->v_count, sizeof(run.look_cnt),
+    c->v_parity = parity ^ 1;
+    EK_HIP(hipMemcpyAsync(run.look_cnt, c->v_count + 2 * parity, sizeof(run.look_cnt),
                           hipMemcpyDeviceToHost, c->stream));
     run.looked = true;
     return EK_OK;
@@ -855,9 +861,9 @@ extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
         return rc;
     uint32_t nv = 0;
     ek_launch_view_select(c->dist, c->n, theta, c->v_blockcnt, c->v_blockoff, c->v_act,
-                          c->view_cap, c->v_count, c->stream);
+                          c->view_cap, c->v_selcnt, c->stream);
     EK_CHECK_LAUNCH();
-    EK_HIP(hipMemcpyAsync(&nv, c->v_count, sizeof(nv), hipMemcpyDeviceToHost, c->stream));
+    EK_HIP(hipMemcpyAsync(&nv, c->v_selcnt, sizeof(nv), hipMemcpyDeviceToHost, c->stream));
     EK_HIP(ek_wait(c));
     out[0] = nv;
     if (nv == 0 || (int64_t)nv > c->view_cap)
@@ -866,13 +872,11 @@ extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
     const size_t tile_words = nt * A3 * EK_TILE;
     const size_t quad_bytes = ek_quad_tiles_bytes((int64_t)nt, c->A);
     // the earlier path into scratch: gather -> frame-minor tiles -> quad copy
-    float *r_aos = nullptr, *r_tiles = nullptr, *r_qtiles = nullptr, *r_dist = nullptr;
+    float *r_tiles = nullptr, *r_qtiles = nullptr, *r_dist = nullptr;
     double *r_G = nullptr;
     int32_t *r_assign = nullptr;
     unsigned long long *diff = nullptr, got[3] = {0, 0, 0};
-    hipError_t e = ek_dev_malloc((void **)&r_aos, (size_t)nv * A3 * sizeof(float));
-    if (e == hipSuccess)
-        e = ek_dev_malloc((void **)&r_tiles, tile_words * sizeof(float));
+    hipError_t e = ek_dev_malloc((void **)&r_tiles, tile_words * sizeof(float));
     if (e == hipSuccess)
         e = ek_dev_malloc((void **)&r_qtiles, quad_bytes);
     if (e == hipSuccess)
@@ -888,8 +892,8 @@ extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
     if (e == hipSuccess)
         e = ek_view_poison(c);
     if (e == hipSuccess) {
-        ek_launch_view_gather(c->v_act, nv, c->A, c->aos, c->G, c->dist, c->assign, r_aos,
-                              r_tiles, r_G, r_dist, r_assign, c->stream);
+        ek_launch_view_gather(c->v_act, nv, c->A, c->aos, c->G, c->dist, c->assign, r_tiles,
+                              r_G, r_dist, r_assign, c->stream);
         ek_launch_quad_tiles(r_tiles, (int64_t)nt, c->A, r_qtiles, c->stream);
         // a rebuild, and the tiles a reader under the view would ask for
         if (!ek_view_build(c, nv))
@@ -897,7 +901,6 @@ extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
         if (c->qt_valid)
             ek_launch_view_diff(c->v_qtiles, r_qtiles, quad_bytes / 4, diff, c->stream);
         ek_launch_view_diff(c->v_tiles, r_tiles, tile_words, diff + 1, c->stream);
-        ek_launch_view_diff(c->v_aos, r_aos, (size_t)nv * A3, diff + 2, c->stream);
         ek_launch_view_diff(c->v_G, r_G, (size_t)nv * 2, diff + 2, c->stream);
         ek_launch_view_diff(c->v_dist, r_dist, (size_t)nv, diff + 2, c->stream);
         ek_launch_view_diff(c->v_assign, r_assign, (size_t)nv, diff + 2, c->stream);
@@ -909,7 +912,6 @@ extern "C" int ek_view_layout_check(ek_ctx *c, float theta, int64_t *out)
         e = ek_wait(c);
     else
         (void)hipStreamSynchronize(c->stream);
-    (void)ek_dev_free(r_aos);
     (void)ek_dev_free(r_tiles);
     (void)ek_dev_free(r_qtiles);
     (void)ek_dev_free(r_G);

@@ -163,7 +163,9 @@ struct EkRound {
     int A, T;
     const float *tiles;
     const float *qtiles;        // quad copy (16-candidate pass; null until one runs)
-    const float *aos;           // the centred frames, frame-major [n][3A]
+    const float *aos;           // the shard's centred frames, frame-major [shard n][3A]
+    const uint32_t *act = nullptr;  // under an active view: the shard row of every position
+                                //   [n]; null: positions are shard rows (ek_round_row)
     const double *G;
     unsigned char *recs;        // T records (kept for the other entry points)
     EkPlan *plan;
@@ -189,6 +191,13 @@ struct EkRound {
     int pick_cap = 4;           // far frames kept per label by the candidate pick (ek_top_dev.h)
     int sweep = 0;              // the pass takes the per-prefix maxima itself (EkFuse::sweep_pm)
 };
+// the frame-major row of position pos of the store the round runs on: a view keeps no
+// frame-major copy of its own, its positions name rows of the shard's (one load of act
+// per row: callers keep the pointer)
+static inline __host__ __device__ const float *ek_round_row(const EkRound &r, size_t pos)
+{
+    return r.aos + (size_t)(r.act ? r.act[pos] : pos) * 3 * r.A;
+}
 // the masks of the round the plan describes (after ek_launch_round_next)
 void ek_launch_round_ti(const EkRound &r, int max_labels, hipStream_t s);
 // with_order: the pass's last workgroup works out the presumed order (single shard)

@@ -355,13 +355,16 @@ struct ek_ctx {
     int view_ratio = 800;            // per mille: build at this share (EK_OPT_VIEW_RATIO)
     bool view_nomem = false;         // there was no memory for it: runs as without
     int64_t view_cap = 0;
-    float *v_aos = nullptr, *v_tiles = nullptr, *v_qtiles = nullptr;
+    float *v_tiles = nullptr, *v_qtiles = nullptr;   // (no frame-major copy: ek_round_row)
     double *v_G = nullptr;
     float *v_dist = nullptr;
     int32_t *v_assign = nullptr;
     uint32_t *v_act = nullptr;       // [view_cap] positions in the shard, ascending
     uint32_t *v_blockcnt = nullptr, *v_blockoff = nullptr;   // select scratch
-    uint32_t *v_count = nullptr;     // [2]
+    uint32_t *v_count = nullptr;     // [4]: a look's two counts, by the look's parity
+    int v_parity = 0;                // of the next look (ek_view_look_kernel): its two words
+                                     //   are zero, the other two the last look's
+    uint32_t *v_selcnt = nullptr;    // [1]: frames of the last selection
     // of the last run: views built, frames x rounds streamed, left out, guard exits
     int64_t view_stats[4] = {0, 0, 0, 0};
 

@@ -347,9 +347,10 @@ ek_round_next_kernel(EkRound r, int bootstrap)
         const int i = w / EK_LIST_M, j = w % EK_LIST_M;
         if (i < j && j < top->n) {
             const int A = r.A;
-            // straight from the frame-major copy: 12 A contiguous bytes each
-            const float *x = r.aos + (size_t)top->idx[i] * 3 * A;
-            const float *y = r.aos + (size_t)top->idx[j] * 3 * A;
+            // straight from the frame-major copy: 12 A contiguous bytes each (under a
+            // view through its selection: one uniform load per row)
+            const float *x = ek_round_row(r, top->idx[i]);
+            const float *y = ek_round_row(r, top->idx[j]);
             float S[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             for (int a = lane; a < A; a += EK_WAVE) {
                 const float x0 = x[3 * a], x1 = x[3 * a + 1], x2 = x[3 * a + 2];
@@ -500,11 +501,18 @@ ek_round_next_kernel(EkRound r, int bootstrap)
     const int A3 = 3 * r.A;
     if (T >= 16 && tid == 0)
         r.plan->n_rec = ns;
-    for (int k0 = 0; T < 16 && k0 * EK_BLOCK < A3; k0 += 4) {
+    // (the chosen frames' rows, looked up once; without a choice the list names no frame)
+    const float *srow[T];
+    if (T < 16 && ns > 0) {
+#pragma unroll
+        for (int c = 0; c < T; ++c)
+            srow[c] = ek_round_row(r, sidx[sel[c < ns ? c : 0]]);
+    }
+    for (int k0 = 0; T < 16 && ns > 0 && k0 * EK_BLOCK < A3; k0 += 4) {
         float v[T][4];
 #pragma unroll
         for (int c = 0; c < T; ++c) {
-            const float *src = r.aos + (size_t)sidx[sel[c < ns ? c : 0]] * A3;
+            const float *src = srow[c];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int row = tid + (k0 + u) * EK_BLOCK;
@@ -573,14 +581,14 @@ __global__ void __launch_bounds__(EK_BLOCK)
 ek_round_ctile16_kernel(EkRound r, int halves)
 {
     typedef float v4 __attribute__((ext_vector_type(4)));
-    __shared__ uint32_t sfr[EK_MAX_CANDS];
+    __shared__ const float *srow[EK_MAX_CANDS];     // the chosen frames' frame-major rows
     const EkPlan *plan = r.plan;
     const int tid = threadIdx.x;
     const int ns = plan->n_rec, go = plan->go;
     if (ns <= 0)
         return;
     if (tid < EK_MAX_CANDS)
-        sfr[tid] = tid < ns ? (uint32_t)(plan->gidx[tid] - r.goff) : 0u;
+        srow[tid] = ek_round_row(r, tid < ns ? (size_t)(plan->gidx[tid] - r.goff) : 0);
     __syncthreads();
     const int A = r.A, A3 = 3 * A;
     const int n_ct = ek_ctile_atoms(A) / 16 * 3;        // (16 atoms, axis) blocks of 1 KB
@@ -591,7 +599,7 @@ ek_round_ctile16_kernel(EkRound r, int halves)
         if (!go || blk >= n_ct || 16 * half >= ns)
             return;
         const int S = blk / 3, k = blk % 3, kk = lane >> 4, c = 16 * half + (lane & 15);
-        const float *src = r.aos + (size_t)sfr[c] * A3 + k;
+        const float *src = srow[c] + k;
         v4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -604,7 +612,7 @@ ek_round_ctile16_kernel(EkRound r, int halves)
         const int c = blockIdx.x - halves * ct_wgs;     // one record per workgroup
         if (c >= ns)
             return;
-        const float *src = r.aos + (size_t)sfr[c] * A3;
+        const float *src = srow[c];
         float *rec = (float *)(r.recs + (size_t)c * ek_rec_bytes(A) + sizeof(EkRecHdr));
         for (int row = tid; row < A3; row += EK_BLOCK)
             rec[row] = src[row];
@@ -745,7 +753,7 @@ ek_round_ti_centers_kernel(EkRound r)
         return;
     const int A = r.A, teff = plan->teff;
     const int64_t f = r.hist[l].gidx - r.goff;
-    const float *x = r.aos + (size_t)f * 3 * A;
+    const float *x = ek_round_row(r, (size_t)f);
     const double Gx = r.G[f];
     const size_t rstride = ek_rec_bytes(A);
     const int c16 = lane & 15, s = lane >> 4;

@@ -13,11 +13,14 @@
 //            offset + its rank inside: positions ascending, no atomics
 //   build    one workgroup per 64 view frames: their frame-major rows
 //            through LDS (as ek_prepare_kernel stages them) into the view's
-//            frame-major copy and its quad copy (ek_view_build_kernel); the
-//            frame-minor tiles only when a kernel that reads them runs under the
-//            view (ek_view_tiles_kernel).  ek_view_gather_kernel is the earlier
-//            form, kept as the reference of ek_view_layout_check
-//   look     the policy's count, theta from the control word on the device
+//            quad copy (ek_view_build_kernel); no frame-major copy: the few rows
+//            a round reads come from the shard's, through the selection
+//            (ek_round_row); the frame-minor tiles only when a kernel that reads
+//            them runs under the view (ek_view_tiles_kernel).
+//            ek_view_gather_kernel is the earlier form, kept as the reference
+//            of ek_view_layout_check
+//   look     the policy's counts, theta from the control word on the device: one
+//            launch over the store being streamed and, under a view, the shard's
 //   scatter  distances and labels back; the centers accepted under the view get
 //            their positions in the shard
 #include <algorithm>
@@ -158,9 +161,8 @@ __global__ void __launch_bounds__(EK_BLOCK)
 ek_view_gather_kernel(const uint32_t *__restrict__ act, int64_t n_v, int A,
                       const float *__restrict__ aos, const double *__restrict__ G,
                       const float *__restrict__ dist, const int32_t *__restrict__ assign,
-                      float *__restrict__ aos_v, float *__restrict__ tiles_v,
-                      double *__restrict__ G_v, float *__restrict__ dist_v,
-                      int32_t *__restrict__ assign_v)
+                      float *__restrict__ tiles_v, double *__restrict__ G_v,
+                      float *__restrict__ dist_v, int32_t *__restrict__ assign_v)
 {
     static_assert(EK_BLOCK == EK_TILE, "one workgroup per tile of the view");
     __shared__ float stage[EK_BLOCK * EK_VIEW_ROWF];
@@ -186,9 +188,7 @@ ek_view_gather_kernel(const uint32_t *__restrict__ act, int64_t n_v, int A,
         // a frame's piece of the chunk is 12 * CH contiguous bytes of its row
         for (int i = t; i < total; i += EK_BLOCK) {
             const int r = i / w, j = i % w;
-            const float v = aos[(size_t)src[r] * A3 + 3 * a0 + j];
-            stage[r * EK_VIEW_ROWF + j] = v;
-            aos_v[(size_t)(p0 + r) * A3 + 3 * a0 + j] = v;
+            stage[r * EK_VIEW_ROWF + j] = aos[(size_t)src[r] * A3 + 3 * a0 + j];
         }
         __syncthreads();
         // frame-minor: 1 KiB per (atom, axis) row of the tile; zeros in the slots
@@ -202,20 +202,20 @@ ek_view_gather_kernel(const uint32_t *__restrict__ act, int64_t n_v, int A,
 
 void ek_launch_view_gather(const uint32_t *act, int64_t n_v, int A, const float *aos,
                            const double *G, const float *dist, const int32_t *assign,
-                           float *aos_v, float *tiles_v, double *G_v, float *dist_v,
-                           int32_t *assign_v, hipStream_t s)
+                           float *tiles_v, double *G_v, float *dist_v, int32_t *assign_v,
+                           hipStream_t s)
 {
     if (n_v <= 0)
         return;
     const unsigned tiles = (unsigned)((n_v + EK_TILE - 1) / EK_TILE);
     hipLaunchKernelGGL(ek_view_gather_kernel, dim3(tiles), dim3(EK_BLOCK), 0, s, act, n_v, A,
-                       aos, G, dist, assign, aos_v, tiles_v, G_v, dist_v, assign_v);
+                       aos, G, dist, assign, tiles_v, G_v, dist_v, assign_v);
 }
 
 // ---------------------------------------------------------------------------
 // build: the gather of a rebuild.  From the staged rows the view's QUAD copy (the
 // layout above ek_quad_tiles_kernel, ek_pass16.hip) instead of its frame-minor tiles:
-// a rebuild then moves a frame three times (one read, two writes), not five.  Without
+// a rebuild then moves a frame twice (one read, one write), not five times.  Without
 // a quad copy in the context (QUAD = false: rounds of 8 at most) the frame-minor
 // tiles, as ek_view_gather_kernel writes them.
 //
@@ -242,9 +242,8 @@ __global__ void __launch_bounds__(EK_BLOCK)
 ek_view_build_kernel(const uint32_t *__restrict__ act, int64_t n_v, int A,
                      const float *__restrict__ aos, const double *__restrict__ G,
                      const float *__restrict__ dist, const int32_t *__restrict__ assign,
-                     float *__restrict__ aos_v, float *__restrict__ out_v,
-                     double *__restrict__ G_v, float *__restrict__ dist_v,
-                     int32_t *__restrict__ assign_v)
+                     float *__restrict__ out_v, double *__restrict__ G_v,
+                     float *__restrict__ dist_v, int32_t *__restrict__ assign_v)
 {
     static_assert(EK_BLOCK == 256 && EK_TILE == 256 && EK_WAVE == 64,
                   "four workgroups per tile of the view, one per wave of the pass");
@@ -295,13 +294,11 @@ ek_view_build_kernel(const uint32_t *__restrict__ act, int64_t n_v, int A,
 #pragma unroll
         for (int it = 0; it < SWEEPS; ++it) {
             const int r = r0 + it * RPS;
-            vec_t *d = (vec_t *)(aos_v + (size_t)(p0 + r) * A3 + 3 * a0);
             float *st = stage + r * EK_VIEW_BROWF;
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
                 const int j = jl + m * LPR;
                 if (r < rows_here && j < we) {
-                    d[j] = v[it][m];
                     if constexpr (VEC == 4) {
 #pragma unroll
                         for (int x = 0; x < 4; ++x)
@@ -350,16 +347,15 @@ ek_view_build_kernel(const uint32_t *__restrict__ act, int64_t n_v, int A,
 
 void ek_launch_view_build(const uint32_t *act, int64_t n_v, int A, bool quad, const float *aos,
                           const double *G, const float *dist, const int32_t *assign,
-                          float *aos_v, float *out_v, double *G_v, float *dist_v,
-                          int32_t *assign_v, hipStream_t s)
+                          float *out_v, double *G_v, float *dist_v, int32_t *assign_v,
+                          hipStream_t s)
 {
     if (n_v <= 0)
         return;
     const unsigned tiles = (unsigned)((n_v + EK_TILE - 1) / EK_TILE);
 #define EK_VIEW_BUILD(VEC, QUAD)                                                          \
     hipLaunchKernelGGL((ek_view_build_kernel<VEC, QUAD>), dim3(4 * tiles), dim3(EK_BLOCK), 0, \
-                       s, act, n_v, A, aos, G, dist, assign, aos_v, out_v, G_v, dist_v,   \
-                       assign_v)
+                       s, act, n_v, A, aos, G, dist, assign, out_v, G_v, dist_v, assign_v)
     if (A % 4 == 0) {
         if (quad)
             EK_VIEW_BUILD(4, true);
@@ -416,13 +412,32 @@ void ek_launch_view_tiles(const float *qtiles, int64_t n_tiles, int A, float *ti
 // maximum the batch left on the device (the host's formula and rounding, ek_api.hip);
 // one atomic per workgroup, a count needs no order.  An estimate only: a view is
 // always built from a theta the host computed.
+//
+// One grid counts both arrays: its first blocks(n) workgroups the store being streamed
+// into mine[0], the rest (under a view) the shard's own distances into mine[1].  The
+// words of the look before, `other`, were read by the host before it enqueued this
+// one: they are zeroed here for the look after, so no look needs a fill of its own.
 // ---------------------------------------------------------------------------
 #define EK_VIEW_LOOK_SEL (8 * EK_VIEW_SEL)     // frames per workgroup of the look
+static inline unsigned ek_view_look_blocks(int64_t n)
+{
+    return n > 0 ? (unsigned)((n + EK_VIEW_LOOK_SEL - 1) / EK_VIEW_LOOK_SEL) : 0u;
+}
+
 __global__ void __launch_bounds__(EK_BLOCK)
-ek_view_look_kernel(const float *__restrict__ dist, int64_t n, const EkCtl *__restrict__ ctl,
-                    double rho, double rel, double abs_, uint32_t *__restrict__ count)
+ek_view_look_kernel(const float *__restrict__ dist_a, int64_t n_a, unsigned blocks_a,
+                    const float *__restrict__ dist_b, int64_t n_b,
+                    const EkCtl *__restrict__ ctl, double rho, double rel, double abs_,
+                    uint32_t *__restrict__ mine_cnt, uint32_t *__restrict__ other)
 {
     __shared__ unsigned red[EK_BLOCK / EK_WAVE];
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        other[0] = other[1] = 0u;
+    const bool second = blockIdx.x >= blocks_a;     // uniform
+    const float *__restrict__ dist = second ? dist_b : dist_a;
+    const int64_t n = second ? n_b : n_a;
+    const int64_t blk = second ? blockIdx.x - blocks_a : blockIdx.x;
+    uint32_t *count = mine_cnt + (second ? 1 : 0);
     const double th = (rho * (double)ctl->last_max - abs_) / (2.0 * (1.0 + rel));
     float theta = (float)th;
     if ((double)theta > th && theta > 0.f)      // (down; at or below zero nobody looks)
@@ -432,8 +447,8 @@ ek_view_look_kernel(const float *__restrict__ dist, int64_t n, const EkCtl *__re
     unsigned mine = 0;
 #pragma unroll
     for (int q = 0; q < EK_VIEW_LOOK_SEL / EK_VIEW_SEL; ++q) {
-        const int64_t f0 = (((int64_t)blockIdx.x * (EK_VIEW_LOOK_SEL / EK_VIEW_SEL) + q) *
-                                EK_BLOCK + threadIdx.x) * EK_VIEW_FPT;
+        const int64_t f0 = ((blk * (EK_VIEW_LOOK_SEL / EK_VIEW_SEL) + q) * EK_BLOCK +
+                            threadIdx.x) * EK_VIEW_FPT;
         mine += f0 < n ? (unsigned)__popc(ek_view_flags(dist, f0, n, theta)) : 0u;
     }
     unsigned total;
@@ -442,14 +457,18 @@ ek_view_look_kernel(const float *__restrict__ dist, int64_t n, const EkCtl *__re
         atomicAdd(count, total);
 }
 
-void ek_launch_view_look(const float *dist, int64_t n, const EkCtl *ctl, double rho, double rel,
-                         double abs_, uint32_t *count, hipStream_t s)
+void ek_launch_view_look(const float *dist, int64_t n, const float *shard_dist,
+                         int64_t shard_n, const EkCtl *ctl, double rho, double rel,
+                         double abs_, uint32_t *count, int parity, hipStream_t s)
 {
-    if (n <= 0)
-        return;
-    hipLaunchKernelGGL(ek_view_look_kernel,
-                       dim3((unsigned)((n + EK_VIEW_LOOK_SEL - 1) / EK_VIEW_LOOK_SEL)),
-                       dim3(EK_BLOCK), 0, s, dist, n, ctl, rho, rel, abs_, count);
+    if (!shard_dist)
+        shard_n = 0;
+    // (never an empty grid: the zeroing of the other parity's words is this launch's too)
+    const unsigned blocks_a = std::max(1u, ek_view_look_blocks(n));
+    hipLaunchKernelGGL(ek_view_look_kernel, dim3(blocks_a + ek_view_look_blocks(shard_n)),
+                       dim3(EK_BLOCK), 0, s, dist, std::max<int64_t>(n, 0), blocks_a, shard_dist,
+                       shard_n, ctl, rho, rel, abs_, count + 2 * (parity & 1),
+                       count + 2 * ((parity & 1) ^ 1));
 }
 
 // words of a[0 .. n) and b[0 .. n) that differ, added to *count (ek_view_layout_check)

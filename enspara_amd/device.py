@@ -594,8 +594,8 @@ class FrameStore:
     def view_layout_check(self, theta):
         """TEST entry: the view of the frames above ``theta`` built as a rebuild builds
         it, against the earlier path's layouts -> (frames in the view, differing words
-        of the quad copy, of the on-demand frame-minor tiles, of the frame-major copy /
-        traces / distances / labels)"""
+        of the quad copy, of the on-demand frame-minor tiles, of the traces / distances
+        / labels)"""
         out = np.zeros(4, dtype=np.int64)
         _lib.check(self.lib.ek_view_layout_check(self._h, float(theta), _lib.i64p(out)))
         return tuple(int(v) for v in out)

@@ -309,9 +309,9 @@ int ek_last_run_form(ek_ctx *ctx, int64_t *out);
  * layouts by the earlier path (gather -> frame-minor tiles -> quad copy), and
  * compares on the device word for word: out[0] frames in the view, out[1] words of the
  * quad copy that differ (whole tiles, padding included; 0 without a quad copy), out[2]
- * words of the frame-minor tiles, out[3] words of the frame-major copy, traces,
- * distances and labels of the live frames.  Not during a run; the run state is left
- * as it was. */
+ * words of the frame-minor tiles, out[3] words of the traces, distances and labels of
+ * the live frames (a view holds no frame-major copy).  Not during a run; the run state
+ * is left as it was. */
 int ek_view_layout_check(ek_ctx *ctx, float theta, int64_t *out);
 
 /* history written by ek_kcenters_step: for labels [first, first+count) the

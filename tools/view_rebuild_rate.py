@@ -3,19 +3,24 @@ every launch of the gather kernels with the frames it moved (its grid: one workg
 256 per tile of the view), its time and the rate that makes of `bytes_per_frame` bytes,
 and the launch counts and total times of the view's other kernels.
 
-    python3 tools/view_rebuild_rate.py <kernel_trace.csv> <atoms> <out.txt>
+    python3 tools/view_rebuild_rate.py <kernel_trace.csv> <atoms> <out.txt> [moves]
+
+`moves`: how many times ek_view_build_kernel moves a frame's 12 * atoms bytes -- 2 in this
+tree (the row read, the quad copy written), 3 for a trace of a tree whose build also wrote a
+frame-major copy of the view (profiles/view_rebuild/).
 """
 import collections
 import csv
 import sys
 
 path, atoms, out = sys.argv[1], int(sys.argv[2]), sys.argv[3]
+moves = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 rows = list(csv.DictReader(open(path)))
 gx = "Grid_Size_X" if rows and "Grid_Size_X" in rows[0] else "Grid_Size"
-# bytes a frame of the view costs: one read of its row, the frame-major copy and the
-# quad copy (ek_view_build_kernel<.., true>), or -- the earlier gather -- the
-# frame-major copy and the frame-minor tile
-per_frame = {"ek_view_build_kernel": 3 * 12 * atoms, "ek_view_gather_kernel": 3 * 12 * atoms}
+# bytes a frame of the view costs: one read of its row and the quad copy
+# (ek_view_build_kernel<.., true>), or -- the earlier gather -- the read, a frame-major
+# copy and the frame-minor tile
+per_frame = {"ek_view_build_kernel": moves * 12 * atoms, "ek_view_gather_kernel": 3 * 12 * atoms}
 tot = collections.defaultdict(lambda: [0, 0.0])
 lines = []
 for r in rows:

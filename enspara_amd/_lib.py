@@ -53,6 +53,7 @@ SYMBOLS = [
     "ek_msm_boot_close",
     "ek_lu_solve", "ek_lu_set_timing", "ek_lu_last_timing",
     "ek_tpt_committors", "ek_tpt_mfpts_sinks", "ek_tpt_mfpts_all", "ek_tpt_fluxes",
+    "ek_tpt_paths_open", "ek_tpt_paths_next", "ek_tpt_paths_stats", "ek_tpt_paths_close",
     "ek_mi_open", "ek_mi_add", "ek_mi_load_counts", "ek_mi_counts", "ek_mi_information",
     "ek_mi_last_timing", "ek_mi_close",
     "ek_cards_open", "ek_cards_add", "ek_cards_stats", "ek_cards_disorder",
@@ -270,6 +271,12 @@ def load():
     L.ek_tpt_mfpts_all.argtypes = [C.c_int, i32, f64p, f64p, C.c_double, f64p, i32p]
     L.ek_tpt_fluxes.argtypes = [C.c_int, i32, f64p, i32p, i32, i32p, i32, f64p, i32, f64p,
                                 f64p, i32p]
+    L.ek_tpt_paths_open.argtypes = [C.c_int, i32, f64p, i64p, i32p, f64p, i32p, i32, i32p, i32,
+                                    i32, i64, C.c_double, C.c_double, i32, i32, i32p,
+                                    C.POINTER(vp)]
+    L.ek_tpt_paths_next.argtypes = [vp, i32p, i32p, f64p, i32p, i32p, i32p]
+    L.ek_tpt_paths_stats.argtypes = [vp, i64p, f64p]
+    L.ek_tpt_paths_close.argtypes = [vp]
     u8p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
     L.ek_mi_open.argtypes = [C.c_int, i32, i32, i32, i32, C.POINTER(vp)]
     L.ek_mi_add.argtypes = [vp, u8p, u8p, i64]

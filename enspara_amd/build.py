@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 OUT = os.path.join(HERE, "libenspara_hip.so")
 SOURCES = ["ek_track.hip", "ek_prepare.hip", "ek_kcenters.hip", "ek_spec.hip", "ek_pass16.hip", "ek_chain.hip", "ek_round.hip", "ek_view.hip", "ek_mshard.hip", "ek_assign.hip", "ek_pam.hip", "ek_pam_sparse.hip",
-           "ek_msm.hip", "ek_msm_boot.hip", "ek_msm_mle.hip", "ek_msm_bace.hip", "ek_lu.hip", "ek_tpt.hip", "ek_mi.hip", "ek_cards.hip", "ek_sasa.hip", "ek_rmsf.hip", "ek_pockets.hip", "ek_wmi.hip", "ek_entropy.hip", "ek_kmc.hip", "ek_rotamer.hip", "ek_krylov.hip", "ek_features.hip", "ek_feat_kcenters.hip", "ek_feat_pam.hip", "ek_feat_pam_shard.hip", "ek_feat_assign.hip", "ek_api.hip", "ek_api_run.hip", "ek_api_pam.hip",
+           "ek_msm.hip", "ek_msm_boot.hip", "ek_msm_mle.hip", "ek_msm_bace.hip", "ek_lu.hip", "ek_tpt.hip", "ek_tpt_path.hip", "ek_mi.hip", "ek_cards.hip", "ek_sasa.hip", "ek_rmsf.hip", "ek_pockets.hip", "ek_wmi.hip", "ek_entropy.hip", "ek_kmc.hip", "ek_rotamer.hip", "ek_krylov.hip", "ek_features.hip", "ek_feat_kcenters.hip", "ek_feat_pam.hip", "ek_feat_pam_shard.hip", "ek_feat_assign.hip", "ek_api.hip", "ek_api_run.hip", "ek_api_pam.hip",
            "ek_api_ms.hip", "ek_dyes.hip", "ek_dye_pair.hip", "ek_dye_bursts.hip", "ek_dye_map.hip"]
 # every header of csrc/, so that none can be forgotten (a stale build followed once)
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".h")) + [

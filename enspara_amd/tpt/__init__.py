@@ -7,9 +7,11 @@ partial pivoting whose trailing update runs on the matrix cores, the
 substitutions and the element-wise epilogues -- is csrc/ek_tpt.hip and
 csrc/ek_lu.hip; a call uploads ``tprob`` once and downloads its result once.
 
-Absent: the reference's ``paths`` and ``top_path`` (enspara/tpt/path.py).  They
-are graph searches on the host with no device work in them; run them on
-``net_fluxes``' output with the reference or with networkx.
+Absent from this namespace, present in a module of their own: the reference's
+``paths`` and ``top_path`` (enspara/tpt/path.py) are
+``enspara_amd.tpt.path.paths`` and ``enspara_amd.tpt.path.top_path``, the
+widest-path searches on the device (csrc/ek_tpt_path.hip); write
+``from enspara_amd.tpt.path import paths`` and hand it ``net_fluxes``' output.
 """
 from .core import committors, mfpts  # noqa: F401
 from .tpt import reactive_fluxes, net_fluxes, reactive_populations  # noqa: F401

@@ -633,6 +633,43 @@ int ek_tpt_fluxes(int device, int32_t n, const double *T, const int32_t *sources
                   int32_t n_sources, const int32_t *sinks, int32_t n_sinks,
                   const double *pops, int32_t net, double *q_out, double *flux_out,
                   int32_t *info_out);
+/* The highest-flux pathways of a net-flux matrix (enspara/tpt/path.py: top_path :46-160,
+ * paths :197-320; csrc/ek_tpt_path.hip states the rule the reference's queue follows).  A
+ * handle keeps the matrix on the device as a CSR of n <= 65535 rows, which removing a path
+ * edits in place, and the running explained flux.  All arrays are host memory.
+ * ek_tpt_paths_open: either dense [n][n] row-major (compacted on the device to its entries
+ * > 0) or, with dense null, CSR arrays: indptr [n + 1] ascending from 0 to nnz < 2^31, cols
+ * [nnz] in [0, n) and strictly ascending within a row, vals [nnz] (entries <= 0 are kept
+ * and never followed).  Finite values are the caller's to check.  sources, sinks: indices
+ * below n, at least one each; repeats and a state in both are allowed.  mode 0 keeps the
+ * matrix and yields one path whatever its flux (top_path: an unreachable sink gives the
+ * sink alone with flux -inf); 1 'subtract' and 2 'bottleneck' remove each path and stop
+ * before a path of infinite flux, or after the one with which the number of paths reaches
+ * num_paths or the sum of flux / total_flux, added up in that order, reaches flux_cutoff.
+ * max_paths, max_nodes: paths (at most 4096) and nodes of one batch, 0 the defaults; a
+ * batch's first path is taken whatever its length.  caps_out (may be null) [2] = the paths
+ * of a batch and the length of nodes_out.  EK_EARG otherwise, also for a dense matrix with
+ * 2^31 or more entries > 0; EK_ENOMEM if the device has not the memory.
+ * ek_tpt_paths_next: the next batch, one launch: *count_out paths, path p = nodes_out[
+ * offsets_out[p] .. offsets_out[p + 1]) from a source to a sink, fluxes_out[p] its flux;
+ * nodes_out [caps[1]], offsets_out [caps[0] + 1], fluxes_out [caps[0]].  *done_out != 0:
+ * no further path follows.  *info_out: 0, or 1 / 2 if a search / a walk back along a path
+ * took more steps than there are states (the handle is done then; neither can happen).
+ * ek_tpt_paths_stats: counts_out[4] = entries of the CSR, pops of all searches, paths
+ * returned, 1 if the searches keep their state in the LDS; ms_out[2] = the compaction's
+ * kernels and the search launches so far, between HIP events. */
+typedef struct ek_tpt_paths ek_tpt_paths;
+int ek_tpt_paths_open(int device, int32_t n, const double *dense, const int64_t *indptr,
+                      const int32_t *cols, const double *vals, const int32_t *sources,
+                      int32_t n_sources, const int32_t *sinks, int32_t n_sinks, int32_t mode,
+                      int64_t num_paths, double total_flux, double flux_cutoff,
+                      int32_t max_paths, int32_t max_nodes, int32_t *caps_out,
+                      ek_tpt_paths **out);
+int ek_tpt_paths_next(ek_tpt_paths *h, int32_t *nodes_out, int32_t *offsets_out,
+                      double *fluxes_out, int32_t *count_out, int32_t *done_out,
+                      int32_t *info_out);
+int ek_tpt_paths_stats(ek_tpt_paths *h, int64_t *counts_out, double *ms_out);
+int ek_tpt_paths_close(ek_tpt_paths *h);
 
 /* ---- joint counts and mutual information of discrete features ----------------------
  * Replaces libinfo.matrix_bincount2d / bincount2d (enspara/info_theory/libinfo.pyx)
